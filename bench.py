@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the 2048 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--chunk 1024]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--chunk 1024] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (with the roofline /
+valu blocks, which come from the same timed region); `--full` adds the sweep, single_step,
+train_loop, urm and cpu_baseline legs below.  `--dump-outputs DIR` writes the trajectory record of
+the last timed step (a fixed seeded sample of the boards, every env step of each) as DIR/<name>.npy;
+the inputs depend only on the arguments, so two builds can be compared output for output.
 
 For N > 1 either launch it under torch.distributed.run (one rank per GPU, RCCL; WORLD_SIZE must
 equal --gpus) or let it hand itself to torch.distributed.run: without WORLD_SIZE in the
@@ -22,6 +29,7 @@ Also reported in the same JSON line:
                  against the HBM peak; the bytes the kernel really moves (26 B per step + 32 B per
                  board per launch) as a separate field; the VALU issue rate from the committed SQ
                  counters of this build, and `bound` = whichever of the two is nearer its peak
+and with --full:
   sweep          the same kernel at 2^20 / 2^22 / 2^24 boards (beyond the 256 MiB Infinity Cache)
   single_step    the one-launch-per-step kernel (env_step_kernel, 42 B/step, §8d) captured in a
                  hipGraph, its steps/s and roofline
@@ -83,6 +91,11 @@ def parse():
     p.add_argument("--sweep", default="1048576,4194304,16777216",
                    help="comma list of board counts for the rollout-kernel sweep ('' = off)")
     p.add_argument("--sweep-chunk", type=int, default=64, help="env steps per launch in the sweep")
+    p.add_argument("--full", action="store_true",
+                   help="also run the sweep, single-step, train-loop, GameURM and CPU-baseline legs (each still has "
+                        "its own switch above); without it only the headline rollout leg runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
     return p.parse_args()
 
 
@@ -438,6 +451,34 @@ def run_sweep(args, rank, world, dev) -> dict:
     return sweep
 
 
+DUMP_BUDGET = 48 << 20  # bytes of float32 per rank's dump (the limit is 64 MB in all)
+DUMP_SEED = 0x2048
+
+
+def dump_outputs(rb, out_dir, rank, world):
+    """--dump-outputs: the trajectory record of the last timed launch (what a caller of
+    env_rollout_random receives: per-step board, action, points, potentials, flags) and the boards it
+    left behind, as float32 .npy files.  The full record is chunk x n x 26 bytes (1.7 GB at the
+    defaults), so a fixed seeded sample of the boards is written, every step of each, with the sampled
+    board indices beside it.  The values are small integers, exact in float32."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    per_board = 4 * (rb.chunk * (16 + 1 + 1 + 4 + 1) + 16 + 1)
+    m = max(1, min(rb.n, DUMP_BUDGET // max(1, world) // per_board))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rb.n, size=m, replace=False))
+    sel = torch.from_numpy(idx).to(rb.tb.device)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    arrays = {"env_index": sel, "final_boards": rb.env.boards.index_select(0, sel),
+              "traj_boards": rb.tb.index_select(1, sel), "traj_actions": rb.ta.index_select(1, sel),
+              "traj_points": rb.tp.index_select(1, sel), "traj_potentials": rb.tpot.index_select(1, sel),
+              "traj_flags": rb.tf.index_select(1, sel)}
+    for name, t in arrays.items():
+        np.save(d / f"{name}{suffix}.npy", t.cpu().numpy().astype(np.float64 if name == "env_index" else np.float32))
+
+
 def main():
     args = parse()
     hand_off_to_ranks(args)  # --gpus N > 1 without a launcher: N fresh ranks, before any GPU call
@@ -454,10 +495,12 @@ def main():
     # graph launches inside the timed region (194.6 vs 186.7 us per launch at K = 200, profiles/r06f)
     rb.capture_exact(args.warmup)
     rb.capture_exact(args.steps)
-    # the sweep and single-step legs (same kernels, other sizes) run before the headline's warm-up and
-    # timed steps, so the headline is not the first GPU work of the process (profiles/r06f/warmup.txt)
-    sweep = run_sweep(args, rank, world, dev) if args.sweep else None
-    single = bench_single_step(args.envs, args.single_steps, rank, dev, world) if args.single_steps > 0 else None
+    # with --full, the sweep and single-step legs (same kernels, other sizes) run before the headline's
+    # warm-up and timed steps, so the headline is not the first GPU work of the process
+    # (profiles/r06f/warmup.txt); a plain run goes straight to the warm-up
+    sweep = run_sweep(args, rank, world, dev) if args.full and args.sweep else None
+    single = (bench_single_step(args.envs, args.single_steps, rank, dev, world)
+              if args.full and args.single_steps > 0 else None)
     rb.run(args.warmup)
     torch.cuda.synchronize()
     wall, ev = time_region(lambda: rb.run(args.steps), 1, world)
@@ -489,6 +532,8 @@ def main():
     }
     if valu:
         result["valu"] = valu
+    if args.dump_outputs:
+        dump_outputs(rb, args.dump_outputs, rank, world)
     del rb
     torch.cuda.empty_cache()
 
@@ -497,17 +542,17 @@ def main():
     if single is not None:
         result["single_step"] = single
 
-    if args.train_iters > 0:
+    if args.full and args.train_iters > 0:
         from g2048 import benchloop
         result["train_loop"] = benchloop.bench_train(args, rank, world, dev)
 
-    if args.urm_steps > 0:
+    if args.full and args.urm_steps > 0:
         from g2048 import benchloop
         result["urm"] = benchloop.bench_urm(args, rank, world, dev)
 
     # the CPU baseline on rank 0's host cores after every GPU leg (at world > 1 the other ranks wait
     # at the barrier below, so the timed GPU regions never share the host with it)
-    if rank == 0 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and args.cpu_seconds > 0:
         cb = cpu_baselines(args.cpu_seconds)
         py = cb.get("python_1core")
         if py:

@@ -8,7 +8,7 @@ cp $LIB /tmp/libg2048_cur.so
 for r in $(seq $R); do
   for v in cur alt; do
     if [ $v = alt ]; then cp $ALT $LIB; else cp /tmp/libg2048_cur.so $LIB; fi
-    timeout -k 10 300 python3 bench.py --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 3 --single-steps 0 --sweep '' --steps 2 --warmup 1 > /tmp/b.log 2>&1
+    timeout -k 10 300 python3 bench.py --full --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 3 --single-steps 0 --sweep '' --steps 2 --warmup 1 > /tmp/b.log 2>&1
     rc=$?; cp /tmp/libg2048_cur.so $LIB; [ $rc -eq 0 ] || { echo "$v rc=$rc"; tail -5 /tmp/b.log; exit 1; }
     python3 -c "
 import json

@@ -38,16 +38,16 @@ env)
   ;;
 fused)
   run_tests $O/tests.log 400 tests/test_gpu_ppo_fused.py
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/trace -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --urm-steps 0 --single-steps 0 --sweep '' > $O/trace.log 2>&1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/trace -o run -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --urm-steps 0 --single-steps 0 --sweep '' > $O/trace.log 2>&1
   rc=$?; echo "trace rc=$rc"; fatal $rc trace
   TAG=${TAG}_fused bash tools/pmc_kernel.sh python3 tools/time_fused.py 65536 > $O/pmc.log 2>&1
   echo "pmc rc=$?"; python3 tools/pmc_table.py gpurun_out/pmck_${TAG}_fused mlp_ 2>&1 | head -60
   ;;
 urm)
   run_tests $O/tests.log 400 tests/test_gpu_urm.py
-  timeout -k 10 300 python3 bench.py --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 3 --single-steps 0 --sweep '' > $O/bench_urm.log 2>&1
+  timeout -k 10 300 python3 bench.py --full --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 3 --single-steps 0 --sweep '' > $O/bench_urm.log 2>&1
   rc=$?; echo "bench rc=$rc"; fatal $rc bench
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/urm -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 1 --single-steps 0 --sweep '' > $O/urm_trace.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $O/urm -o run -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --train-iters 0 --urm-steps 16 --urm-iters 1 --single-steps 0 --sweep '' > $O/urm_trace.log 2>&1
   rc=$?; echo "urm trace rc=$rc"; fatal $rc urm
   timeout -k 10 400 python3 tools/prof_urm_ops.py 65536 16 > $O/prof_ops.log 2>&1
   echo "census rc=$?"
@@ -83,7 +83,7 @@ full)
   run_tests $O/tests.log 700 tests
   timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
   rc=$?; echo "smoke rc=$rc"; tail -1 $O/smoke.log; fatal $rc smoke
-  timeout -k 10 600 python3 bench.py > $O/bench.log 2>&1
+  timeout -k 10 600 python3 bench.py --full > $O/bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; fatal $rc bench
   ;;
 *) echo "usage: TAG=... bash tools/gpu/check.sh env|fused|urm|full"; exit 2 ;;

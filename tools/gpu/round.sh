@@ -13,6 +13,7 @@ if [ -z "$SKIP_TESTS" ]; then
   [ $rc -eq 0 ] || [ -n "$CONTINUE_ON_FAIL" ] || exit $rc
 fi
 if [ -z "$SKIP_BENCH" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS}"  # the default line with every leg
   timeout -k 10 600 python bench.py ${BENCH_ARGS} > gpurun_out/bench_$TAG.log 2>&1
   rc=$?; echo "bench rc=$rc"; tail -c 3000 gpurun_out/bench_$TAG.log
   [ $rc -eq 0 ] || exit $rc

@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/r06c; mkdir -p $O
-timeout -k 10 240 rocprofv3 --kernel-trace -T --output-format csv -d $O/trace -o run -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --urm-steps 0 --single-steps 0 --sweep= --train-iters 1 --train-warmup 1 > $O/trace.log 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace -T --output-format csv -d $O/trace -o run -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --urm-steps 0 --single-steps 0 --sweep= --train-iters 1 --train-warmup 1 > $O/trace.log 2>&1
 echo rc=$?
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 tools/timeline.py $f mlp_back_kernel > $O/timeline.txt; cat $O/timeline.txt

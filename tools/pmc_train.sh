@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 TAG=${TAG:-r03}
 URMS=${URM:+8}
-ARGS=${ARGS:---steps 2 --warmup 1 --cpu-seconds 0 --single-steps 0 --train-iters 1 --train-warmup 1 --urm-steps ${URMS:-0} --sweep=}
+ARGS=${ARGS:---full --steps 2 --warmup 1 --cpu-seconds 0 --single-steps 0 --train-iters 1 --train-warmup 1 --urm-steps ${URMS:-0} --sweep=}
 OUT=gpurun_out/ptrain_$TAG
 mkdir -p $OUT
 # progress line every 50 s (PMC passes write nothing until they finish): the pass output sizes so far
