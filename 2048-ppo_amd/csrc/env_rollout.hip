@@ -16,54 +16,50 @@ using namespace g2048;
 
 namespace {
 
-__device__ const lut::Row12Table kRow12 __attribute__((aligned(16))) = lut::Row12Table();
-__device__ const lut::Line12Table kLine12 __attribute__((aligned(16))) = lut::Line12Table();
+__device__ const lut::Line11Table kLine11 __attribute__((aligned(16))) = lut::Line11Table();
+static_assert(lut::line11_table_ok(lut::Line11Table()), "kLine11 fields against slide_entry / line_entry");
 
-// LDS layout of env_rollout_kernel: kLine12 at byte 0 (41 KiB, so a line's byte address 2 idx fits
-// in 16 bits and four of them come out of packed-u16 arithmetic), kRow12 right after it.  Lanes
-// whose board holds an exponent >= 12 still issue the (discarded) table reads with 4-bit-masked
-// digits, i.e. indices up to 15 * 1885 = 28 275: a kLine12 read may then land in kRow12 and a
-// kRow12 read in kFresh (harmless: both inside the allocation).
-constexpr uint32_t kRowLds = lut::kLineEntriesPadded * 2u;                   // 41 984
-// then the auto-reset boards and their statistics (kFresh)
+// LDS layout of env_rollout_kernel: kLine11 at byte 0 (8-byte records, 115 KiB with its padding),
+// then the auto-reset boards (kFresh), the addresses of their line records (kFreshLines) and their
+// statistics.
 __device__ const lut::FreshTable kFresh __attribute__((aligned(16))) = lut::FreshTable();
-constexpr uint32_t kFreshBoardBase = 137u * 1024u;                          // 15 KiB of boards
-constexpr uint32_t kFreshStatBase = kFreshBoardBase + lut::kFreshEntries * 16u;  // 4 KiB of stats
-constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 4096u) / 4u;         // 159 744 B
-static_assert(kRowLds + lut::kRowEntries * 4u <= kFreshBoardBase, "kRow12 below kFresh");
-static_assert(kRowLds + 4u * 28276u <= kRolloutLdsWords * 4u, "masked kRow12 reads stay inside the allocation");
-// kLine12 reads take unmasked digits (line12_addrs): exponents <= 17 and the spawn's + 2 x 2 x 12^3
-static_assert(2u * 17u * 1885u + 2u * 2u * 1728u + 2u <= kRolloutLdsWords * 4u, "kLine12 reads stay inside the allocation");
-static_assert(2u * (lut::kRowEntries - 1u) < 65536u, "kLine12 byte addresses fit 16 bits");
+__device__ const lut::FreshLineTable kFreshLines __attribute__((aligned(16))) = lut::FreshLineTable();
+static_assert(lut::fresh_lines_ok(lut::FreshTable(), lut::FreshLineTable()), "kFreshLines against the kFresh boards");
+constexpr uint32_t kLineLdsBytes = lut::kFusedEntriesPadded * 8u;             // 117 760
+constexpr uint32_t kFreshBoardBase = kLineLdsBytes;                           // 15 KiB of boards
+constexpr uint32_t kFreshLineBase = kFreshBoardBase + lut::kFreshEntries * 16u;  // 15 KiB of line addresses
+constexpr uint32_t kFreshStatBase = kFreshLineBase + lut::kFreshEntries * 16u;   // 4 KiB of stats
+constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 4096u) / 4u;          // 152 576 B
+static_assert(kRolloutLdsWords * 4u <= 160u * 1024u, "the tables fit the 160 KiB of LDS");
+// Every LDS address the kernel forms:
+//  - a kLine11 record at 8 idx (8 bytes, or the u16 at + 4) with every digit of the line <= 10.  The
+//    wave-uniform fast pair starts with every exponent <= 8 and a move adds at most 1 to the maximum,
+//    so its two steps index boards of exponents <= 9 and <= 10; every other step zeroes the board it
+//    takes addresses from in the lanes that hold an exponent > 10 (their reads are discarded), and
+//    the spawn's pre-spawn lines are the post-spawn ones minus the spawned digit.
+constexpr uint32_t kMaxLineDigit = lut::kLineBase - 1u;
+static_assert(8u * lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) + 8u <= lut::kFusedEntries * 8u &&
+              lut::kFusedEntries * 8u <= kLineLdsBytes, "kLine11 reads stay inside the table");
+static_assert(8u + 1u + 1u <= kMaxLineDigit, "a fast pair (start <= 8) stays inside kLine11");
+static_assert(lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) < 65536u, "column indices fit the packed-u16 sums");
+//  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry above)
+static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line records inside kLine11");
+//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of board, 16 B of line
+//    addresses, 4 B of statistics
+static_assert(60u * 15u + 4u * 14u + 3u == lut::kFreshEntries - 1u, "kFresh index range");
+static_assert(kFreshStatBase + 4u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
 
 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u16x2 as_u16x2(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
 
-// LDS byte address of the kRow12 entry of a LEFT-frame row dword (byte j = cell j):
-// kRowLds + 4 (c0 + 12 c1 + 144 c2 + 1728 c3) as two packed-u16 dot products.  Bytes are masked
-// to 4 bits so any row (even one holding exponents >= 12, whose lane takes the compute path)
-// addresses inside the LDS allocation (< kRowLds + 15 * 1885 * 4 bytes).
-// kSmall (every exponent <= 10): the digits need no mask, so each pair is one byte-select v_perm
-template <bool kSmall = false>
-__device__ __forceinline__ uint32_t row12_addr(uint32_t x) {
-    const u16x2 k02 = {4, 576}, k13 = {48, 6912};
-    const uint32_t a = kSmall ? __builtin_amdgcn_perm(0u, x, 0x0C020C00u) : x & 0x000F000Fu;         // cells 0, 2
-    const uint32_t b = kSmall ? __builtin_amdgcn_perm(0u, x, 0x0C030C01u) : (x >> 8) & 0x000F000Fu;  // cells 1, 3
-    return __builtin_amdgcn_udot2(as_u16x2(b), k13, __builtin_amdgcn_udot2(as_u16x2(a), k02, kRowLds, false), false);
-}
-__device__ __forceinline__ uint32_t lds_word(const uint32_t *tab, uint32_t addr) {
-    return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(tab) + addr);
-}
-// LDS byte addresses (2 idx) of the kLine12 entries of a board's four rows (a row read left to
-// right) and four columns (top to bottom), from the rows' 4-bit digit pairs: A_i = cells (i, 0) and
-// (i, 2), B_i = cells (i, 1) and (i, 3) as u16 halves.  Rows: two packed-u16 dot products each.
-// Columns: column pairs (0, 2) and (1, 3) at once as packed-u16 multiply-adds over the rows,
-// 2 (cell(0, j) + 12 cell(1, j) + 144 cell(2, j) + 1728 cell(3, j)) < 2^16 per half -- no transpose.
-// The digit pairs are the bytes themselves (one v_perm each, no 4-bit mask): a board of the SWAR
-// fallback (exponents up to 17) gives indices up to 2 x 17 x 1885 = 64 090 bytes, inside the LDS
-// allocation (its reads are discarded), and no u16 sum below overflows.
-__device__ __forceinline__ void line12_addrs(const uint4 &b, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
-    const u16x2 k02 = {2, 288}, k13 = {24, 3456};
+// LDS byte addresses (8 idx) of the kLine11 records of a board's four rows (a row read left to
+// right) and four columns (top to bottom), from the rows' digit pairs: A_i = cells (i, 0) and
+// (i, 2), B_i = cells (i, 1) and (i, 3) as u16 halves (the bytes themselves, one v_perm each: every
+// exponent of the board is <= 10).  Rows: two packed-u16 dot products each, weights 8 x 11^j.
+// Columns: column pairs (0, 2) and (1, 3) at once as packed-u16 multiply-adds over the rows; the
+// byte address (up to 117 120) does not fit 16 bits, so the halves hold idx and are scaled after.
+__device__ __forceinline__ void line11_addrs(const uint4 &b, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
+    const u16x2 k02 = {8, 968}, k13 = {88, 10648};
     const uint32_t w[4] = {b.x, b.y, b.z, b.w};
     u16x2 A[4], B[4];
 #pragma unroll
@@ -72,35 +68,34 @@ __device__ __forceinline__ void line12_addrs(const uint4 &b, uint32_t (&ra)[4], 
         B[i] = as_u16x2(__builtin_amdgcn_perm(0u, w[i], 0x0C030C01u));
         ra[i] = __builtin_amdgcn_udot2(B[i], k13, __builtin_amdgcn_udot2(A[i], k02, 0u, false), false);
     }
-    const u16x2 c02 = A[0] * (u16x2){2, 2} + A[1] * (u16x2){24, 24} + A[2] * (u16x2){288, 288} + A[3] * (u16x2){3456, 3456};
-    const u16x2 c13 = B[0] * (u16x2){2, 2} + B[1] * (u16x2){24, 24} + B[2] * (u16x2){288, 288} + B[3] * (u16x2){3456, 3456};
+    const u16x2 c02 = A[0] + A[1] * (u16x2){11, 11} + A[2] * (u16x2){121, 121} + A[3] * (u16x2){1331, 1331};
+    const u16x2 c13 = B[0] + B[1] * (u16x2){11, 11} + B[2] * (u16x2){121, 121} + B[3] * (u16x2){1331, 1331};
     const uint32_t p02 = __builtin_bit_cast(uint32_t, c02), p13 = __builtin_bit_cast(uint32_t, c13);
-    ca[0] = p02 & 0xFFFFu;
-    ca[1] = p13 & 0xFFFFu;
-    ca[2] = p02 >> 16;
-    ca[3] = p13 >> 16;
+    ca[0] = (p02 & 0xFFFFu) << 3;
+    ca[1] = (p13 & 0xFFFFu) << 3;
+    ca[2] = (p02 >> 16) << 3;
+    ca[3] = (p13 >> 16) << 3;
+}
+__device__ __forceinline__ uint2 lds_rec(const uint32_t *tab, uint32_t addr) {
+    return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(tab) + addr);
 }
 __device__ __forceinline__ uint32_t lds_half(const uint32_t *tab, uint32_t addr) {
     return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(tab) + addr);
 }
-// byte-reverse each row when the lane's selector says so (one v_perm per row, no select)
-__device__ __forceinline__ uint4 perm4(const uint4 &w, uint32_t sel) {
-    return make_uint4(__builtin_amdgcn_perm(w.x, w.x, sel), __builtin_amdgcn_perm(w.y, w.y, sel),
-                      __builtin_amdgcn_perm(w.z, w.z, sel), __builtin_amdgcn_perm(w.w, w.w, sel));
-}
 
-// nibble-packed row (bits 0..15 of a table entry) -> row dword with one exponent per byte, byte
-// reversed or not by the lane's selector: nibble j is the low nibble of byte j/2 of e (j even) or of
-// e >> 4 (j odd), so one v_perm over (e >> 4, e) places all four and a mask clears the high nibbles.
-constexpr uint32_t kUnpackSel = 0x05010400u;     // bytes {n0, n1, n2, n3}
-constexpr uint32_t kUnpackRevSel = 0x00040105u;  // bytes {n3, n2, n1, n0}
+// nibble-packed line (dword 0 of a kLine11 record) -> line dword with one exponent per byte, the
+// start-slid half (bits 0..15) or the end-slid half (bits 16..31) by the lane's selector: nibble j of
+// a half is the low nibble of byte j/2 of e (j even) or of e >> 4 (j odd), so one v_perm over
+// (e >> 4, e) places all four and a mask clears the high nibbles.
+constexpr uint32_t kUnpackStartSel = 0x05010400u;  // bytes {n0, n1, n2, n3}
+constexpr uint32_t kUnpackEndSel = 0x07030602u;    // bytes {n4, n5, n6, n7}
 __device__ __forceinline__ uint32_t unpack_row(uint32_t e, uint32_t sel) {
     return __builtin_amdgcn_perm(e >> 4, e, sel) & 0x0F0F0F0Fu;
 }
 
 // Packed monotonicity statistics of the rollout kernel, one VGPR per board: bits 0..3 pos (the
 // first row-major cell holding the maximum), 8..11 L, 12..15 R, 16..19 T, 20..23 B (board.hpp
-// MonoStats), 24..27 M.  Bytes 1 and 2 are the low bytes of a board's kLine12 row / column sums.
+// MonoStats), 24..27 M.  Bytes 1 and 2 are the low bytes of a board's kLine11 row / column line-entry sums.
 __device__ __forceinline__ uint32_t pack_stats(const MonoStats &s) {
     return s.pos | ((uint32_t)s.L << 8) | ((uint32_t)s.R << 12) | ((uint32_t)s.T << 16) | ((uint32_t)s.B << 20) |
            (s.M << 24);
@@ -114,7 +109,7 @@ __device__ __forceinline__ uint32_t mono_value_packed(uint32_t S) {
     const uint32_t corner = __builtin_amdgcn_ubfe(0x9009u, S, 1u);
     return best256 >> (9u - 2u * corner);
 }
-// L|R and T|B bytes of a board's kLine12 row sum SR and column sum SC into bytes 1 and 2
+// L|R and T|B bytes of a board's kLine11 row sum SR and column sum SC into bytes 1 and 2
 __device__ __forceinline__ uint32_t stats_bytes(uint32_t SR, uint32_t SC) {
     return __builtin_amdgcn_perm(SC, SR, 0x0C04000Cu);
 }
@@ -177,40 +172,32 @@ __device__ __forceinline__ uint32_t fresh_stats(uint32_t p1, uint32_t v1, uint32
     return legal;
 }
 
-// Copy the tables (kLine12, kRow12, kFresh) into LDS by LDS-DMA: each wave instruction moves 1 KiB (16 B per lane)
+// Copy the tables (kLine11, kFresh, kFreshLines) into LDS by LDS-DMA: each wave instruction moves 1 KiB (16 B per lane)
 // straight from global memory into LDS with no VGPR staging, and every piece of the wave is in
 // flight before the single wait (one L2/MALL round trip per launch instead of one per batch).
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glb_void_t;
 __device__ __forceinline__ void stage_row_table(uint32_t *s_row) {
-    constexpr int kPieces = (int)(lut::kRowEntries * 4u / 1024u);  // 81 pieces of 1 KiB
-    constexpr int kLinePieces = (int)(lut::kLineEntriesPadded * 2u / 1024u);  // + 41 of kLine12
-    constexpr int kFreshPieces = (int)(lut::kFreshEntries * 16u / 1024u);  // + 15 boards + 4 stats
-    static_assert(lut::kRowEntries * 4u % 1024u == 0u && lut::kLineEntriesPadded * 2u % 1024u == 0u &&
-                  lut::kFreshEntries * 16u % 1024u == 0u, "whole 1 KiB pieces");
-    constexpr int kAll = kPieces + kLinePieces + kFreshPieces + 4;
-    const char *src = reinterpret_cast<const char *>(kLine12.v);  // pieces 0 .. kLinePieces - 1
-    const char *src2 = reinterpret_cast<const char *>(kRow12.v);
-    const char *src3 = reinterpret_cast<const char *>(kFresh.b);
+    constexpr int kLinePieces = (int)(kLineLdsBytes / 1024u);                 // 115 pieces of 1 KiB
+    constexpr int kFreshPieces = (int)(lut::kFreshEntries * 16u / 1024u);     // + 15 boards + 15 line addresses + 4 stats
+    static_assert(kLineLdsBytes % 1024u == 0u && lut::kFreshEntries * 16u % 1024u == 0u, "whole 1 KiB pieces");
+    static_assert(sizeof(kLine11.v) == kLineLdsBytes && sizeof(kFresh.b) == kFreshPieces * 1024 &&
+                  sizeof(kFreshLines.a) == kFreshPieces * 1024 && sizeof(kFresh.st) == 4096, "table sizes");
+    constexpr int kAll = kLinePieces + 2 * kFreshPieces + 4;  // the LDS layout is the pieces in this order
+    static_assert(kAll * 1024 == (int)(kRolloutLdsWords * 4u), "the pieces fill the allocation");
+    const char *src = reinterpret_cast<const char *>(kLine11.v);
+    const char *src2 = reinterpret_cast<const char *>(kFresh.b);
+    const char *src3 = reinterpret_cast<const char *>(kFreshLines.a);
     const char *src4 = reinterpret_cast<const char *>(kFresh.st);
     char *dst = reinterpret_cast<char *>(s_row);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int c = wave; c < kAll; c += nw) {
         const char *g;
-        uint32_t d;
-        if (c < kPieces + kLinePieces) {  // kLine12 at 0, then kRow12 at kRowLds (= kLinePieces KiB)
-            g = c < kLinePieces ? src + 1024 * c : src2 + 1024 * (c - kLinePieces);
-            d = 1024u * (uint32_t)c;
-        } else if (c < kPieces + kLinePieces + kFreshPieces) {
-            const int k = c - kPieces - kLinePieces;
-            g = src3 + 1024 * k;
-            d = kFreshBoardBase + 1024u * (uint32_t)k;
-        } else {
-            const int k = c - kPieces - kLinePieces - kFreshPieces;
-            g = src4 + 1024 * k;
-            d = kFreshStatBase + 1024u * (uint32_t)k;
-        }
-        __builtin_amdgcn_global_load_lds((glb_void_t *)(g + 16 * lane), (lds_void_t *)(dst + d), 16, 0, 0);
+        if (c < kLinePieces) g = src + 1024 * c;
+        else if (c < kLinePieces + kFreshPieces) g = src2 + 1024 * (c - kLinePieces);
+        else if (c < kLinePieces + 2 * kFreshPieces) g = src3 + 1024 * (c - kLinePieces - kFreshPieces);
+        else g = src4 + 1024 * (c - kLinePieces - 2 * kFreshPieces);
+        __builtin_amdgcn_global_load_lds((glb_void_t *)(g + 16 * lane), (lds_void_t *)(dst + 1024 * c), 16, 0, 0);
     }
     __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) lgkmcnt(0): this wave's pieces have landed
     __syncthreads();
@@ -222,6 +209,8 @@ struct RolloutLane {
     uint32_t legal;   // its legal mask
     uint32_t S;       // its packed monotonicity statistics (pack_stats)
     int empt_b;       // its empty-cell count
+    uint2 R[4], C[4]; // the kLine11 records of its rows and columns (valid while its maximum is <= 10;
+                      // a board above that moves on the SWAR path, which does not read them)
     uint4 D;          // Philox draw of the current pair of steps: x / y = the two steps' words,
                       // z / w = the words of a reset inside the pair (at most one: a reset board
                       // cannot end again one move later)
@@ -229,10 +218,13 @@ struct RolloutLane {
     uint4 fb;         // the board a reset inside the current pair starts (D.z, D.w -> kFresh) ...
     uint32_t flegal;  // ... its legal mask and packed statistics
     uint32_t fS;
+    uint4 fla;        // ... the LDS addresses of the kLine11 records of its rows and columns (8 x u16) ...
+    uint2 fR[4], fC[4];  // ... and those records, read one step after the addresses (fresh_lines)
 };
 
 // the current pair's auto-reset board from kFresh (fresh_from_pair's board and fresh_stats' results,
-// read once per pair right after the draw is known, long before a step can need them)
+// read once per pair right after the draw is known, long before a step can need them), and the
+// addresses of the records of its eight lines (kFreshLines)
 __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__restrict__ tab) {
     const uint32_t a = s.D.z, bw = s.D.w;
     const uint64_t pb = (uint64_t)bw * 15u;  // one v_mad_u64_u32: k2 and the low word
@@ -241,9 +233,36 @@ __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__res
                        ((uint32_t)pb >= kTwoThreshold ? 1u : 0u);
     const char *t = reinterpret_cast<const char *>(tab);
     s.fb = *reinterpret_cast<const uint4 *>(t + kFreshBoardBase + 16u * i);
+    s.fla = *reinterpret_cast<const uint4 *>(t + kFreshLineBase + 16u * i);
     const uint32_t st = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
     s.flegal = st >> 28;
     s.fS = st & 0x0FFFFFFFu;
+}
+// ... and the records themselves, one step later: issued with the even step's own table reads, so
+// that the second of the two dependent reads adds no LDS round trip of its own
+__device__ __forceinline__ void fresh_lines(RolloutLane &s, const uint32_t *__restrict__ tab) {
+    const uint4 la = s.fla;
+    s.fR[0] = lds_rec(tab, la.x & 0xFFFFu);
+    s.fR[1] = lds_rec(tab, la.x >> 16);
+    s.fR[2] = lds_rec(tab, la.y & 0xFFFFu);
+    s.fR[3] = lds_rec(tab, la.y >> 16);
+    s.fC[0] = lds_rec(tab, la.z & 0xFFFFu);
+    s.fC[1] = lds_rec(tab, la.z >> 16);
+    s.fC[2] = lds_rec(tab, la.w & 0xFFFFu);
+    s.fC[3] = lds_rec(tab, la.w >> 16);
+}
+
+// the records of the current board's lines from the board itself (launch start; the steps keep them
+// up to date from then on).  A lane whose board holds an exponent > 10 reads the empty line's.
+__device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__restrict__ tab) {
+    const uint4 ab = sel4((s.S >> 24) > kMaxLineDigit, make_uint4(0u, 0u, 0u, 0u), s.b);
+    uint32_t ra[4], ca[4];
+    line11_addrs(ab, ra, ca);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        s.R[i] = lds_rec(tab, ra[i]);
+        s.C[i] = lds_rec(tab, ca[i]);
+    }
 }
 
 struct TrajRows {  // this lane's element of row t of each time-major trajectory array (advanced by n per step)
@@ -272,26 +291,23 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const uint32_t u = kOdd ? s.D.y : s.D.x;
     const uint64_t pa = (uint64_t)u * (uint32_t)__popc(s.legal);
     const uint32_t a = kth_bit4(s.legal, (uint32_t)(pa >> 32)), r = (uint32_t)pa;
-    // the move through the LDS row table in the LEFT frame.  Half of the next pair's Philox rounds
-    // fill the LDS round trip: the empty asm statements start them after the table loads are issued
-    // (memory clobber) and consume the loaded entries after them.
-    const bool vert = a < 2u, rev = (a & 1u) != 0u;  // DOWN / RIGHT: byte-reversed rows
-    const uint32_t rsel = rev ? 0x00010203u : 0x03020100u, usel = rev ? kUnpackRevSel : kUnpackSel;
-    uint4 w = perm4(sel4(vert, transpose(s.b), s.b), rsel);
-    uint32_t e0 = lds_word(tab, row12_addr<kSmall>(w.x)), e1 = lds_word(tab, row12_addr<kSmall>(w.y));
-    uint32_t e2 = lds_word(tab, row12_addr<kSmall>(w.z)), e3 = lds_word(tab, row12_addr<kSmall>(w.w));
-    asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3)::"memory");
-    if constexpr (kOdd) philox_rounds<5, 10>(s.ph);
-    else philox_rounds<0, 5>(s.ph);
-    asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3), "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
+    // the move from the carried records: the columns' for UP / DOWN, the rows' otherwise; the
+    // start-slid half for UP / LEFT, the end-slid one for DOWN / RIGHT (the unpack selector).  No
+    // table read and no address arithmetic: the previous step read these records.
+    const bool vert = a < 2u, rev = (a & 1u) != 0u;
+    const uint32_t usel = rev ? kUnpackEndSel : kUnpackStartSel;
+    const uint32_t e0 = vert ? s.C[0].x : s.R[0].x, e1 = vert ? s.C[1].x : s.R[1].x;
+    const uint32_t e2 = vert ? s.C[2].x : s.R[2].x, e3 = vert ? s.C[3].x : s.R[3].x;
+    const uint32_t h0 = vert ? s.C[0].y : s.R[0].y, h1 = vert ? s.C[1].y : s.R[1].y;
+    const uint32_t h2 = vert ? s.C[2].y : s.R[2].y, h3 = vert ? s.C[3].y : s.R[3].y;
     const uint32_t mono_b = mono_value_packed(s.S);
-    w = make_uint4(unpack_row(e0, usel), unpack_row(e1, usel), unpack_row(e2, usel), unpack_row(e3, usel));
+    const uint4 w = make_uint4(unpack_row(e0, usel), unpack_row(e1, usel), unpack_row(e2, usel), unpack_row(e3, usel));
     uint4 moved = sel4(vert, transpose(w), w);
-    // merge points / 4 in bits 16..27 of each entry, the slid row's maximum in bits 28..31
-    uint32_t pts = (((e0 >> 16) & 0xFFFu) + ((e1 >> 16) & 0xFFFu) + ((e2 >> 16) & 0xFFFu) + ((e3 >> 16) & 0xFFFu)) << 2;
-    uint32_t Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(e0), as_u16x2(e1)),
-                                                                         __builtin_elementwise_max(as_u16x2(e2), as_u16x2(e3)))) >> 28;
-    if (!kSmall && (s.S >> 24) > 11u) {  // an exponent outside the table: the SWAR compute path
+    // merge points / 4 in bits 16..27 of each record's dword 1, the slid line's maximum in bits 28..31
+    uint32_t pts = (((h0 >> 16) & 0xFFFu) + ((h1 >> 16) & 0xFFFu) + ((h2 >> 16) & 0xFFFu) + ((h3 >> 16) & 0xFFFu)) << 2;
+    uint32_t Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(h0), as_u16x2(h1)),
+                                                                         __builtin_elementwise_max(as_u16x2(h2), as_u16x2(h3)))) >> 28;
+    if (!kSmall && (s.S >> 24) > kMaxLineDigit) {  // an exponent outside the table: the SWAR compute path
         uint32_t mx;
         moved = apply_move(s.b, a, pts, mx);
         Ma = board_max(moved);
@@ -299,12 +315,6 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const uint32_t rm[4] = {moved.x, moved.y, moved.z, moved.w};
     const uint32_t Zm[4] = {zm(moved.x), zm(moved.y), zm(moved.z), zm(moved.w)};
     const uint32_t pos_a = first_cell_eq(rm, Ma);
-    // the moved board's (pre-spawn) lines in kLine12: four rows and four columns, read before the
-    // spawn is known; the spawn then changes one row and one column, read again below
-    uint32_t ra[4], ca[4];
-    line12_addrs(moved, ra, ca);
-    const uint32_t f0 = lds_half(tab, ra[0]), f1 = lds_half(tab, ra[1]), f2 = lds_half(tab, ra[2]), f3 = lds_half(tab, ra[3]);
-    const uint32_t g0 = lds_half(tab, ca[0]), g1 = lds_half(tab, ca[1]), g2 = lds_half(tab, ca[2]), g3 = lds_half(tab, ca[3]);
     // spawn on the k-th empty cell (row-major), k = floor(r * empties / 2^32), value 1 if the low
     // word of r * empties is below 0.9 * 2^32 (given k that low word is uniform to within
     // empties / 2^32); the row from the prefix counts of empties, the column inside the row likewise
@@ -327,20 +337,43 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     moved.z |= (r2 && !r3) ? bits : 0u;
     moved.w |= r3 ? bits : 0u;
     s.b = moved;  // the next board (after the spawn)
-    // the spawn's row and column in the next board: kLine12 byte address + v * 2 * 12^(column / row)
-    constexpr uint64_t kW12 = 0x0D80012000180002ull;  // {2, 24, 288, 3456}
-    const uint32_t rp = r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0], cp = c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];
-    const uint32_t rq = rp + v * ((uint32_t)(kW12 >> (16u * col)) & 0xFFFFu);
-    const uint32_t cq = cp + v * ((uint32_t)(kW12 >> (16u * row)) & 0xFFFFu);
-    // the spawn row / column entries after the spawn (the last LDS round trip of the step: two reads)
-    // and before it (selected among f0..g3, which have landed by now)
-    const uint32_t fq = lds_half(tab, rq), gq = lds_half(tab, cq);
-    const uint32_t fp = r3 ? f3 : r2 ? f2 : r1 ? f1 : f0, gp = c3 ? g3 : c2 ? g2 : c1 ? g1 : g0;
+    // The step's one LDS round trip: the records of the next board's four rows and four columns (the
+    // next move, whatever its direction, and this board's line sums), and the line entries of the
+    // spawn's row and column before and after the spawn (dword 1's low half), whose difference
+    // takes the sums back to the moved board's.  The pre-spawn address is the post-spawn one minus
+    // v x 8 x 11^(column / row).  Outside the fast pair a lane holding an exponent > 10 takes its
+    // addresses from an empty board (its reads are discarded below).
+    uint4 ab = moved;
+    uint32_t va = v;
+    if (!kSmall) {
+        const bool big = Ma > kMaxLineDigit;
+        ab = sel4(big, make_uint4(0u, 0u, 0u, 0u), moved);
+        va = big ? 0u : v;
+    }
+    uint32_t ra[4], ca[4];
+    line11_addrs(ab, ra, ca);
+    constexpr uint64_t kW11 = 0x299803C800580008ull;  // 8 x {1, 11, 121, 1331}
+    const uint32_t rq = r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0], cq = c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];
+    const uint32_t rp = rq - va * ((uint32_t)(kW11 >> (16u * col)) & 0xFFFFu);
+    const uint32_t cp = cq - va * ((uint32_t)(kW11 >> (16u * row)) & 0xFFFFu);
+    uint2 R0 = lds_rec(tab, ra[0]), R1 = lds_rec(tab, ra[1]), R2 = lds_rec(tab, ra[2]), R3 = lds_rec(tab, ra[3]);
+    uint2 C0 = lds_rec(tab, ca[0]), C1 = lds_rec(tab, ca[1]), C2 = lds_rec(tab, ca[2]), C3 = lds_rec(tab, ca[3]);
+    uint32_t fq = lds_half(tab, rq + 4u), gq = lds_half(tab, cq + 4u);
+    uint32_t fp = lds_half(tab, rp + 4u), gp = lds_half(tab, cp + 4u);
+    // half of the next pair's Philox rounds fill the round trip: the empty asm statements start them
+    // after the table loads are issued (memory clobber) and consume the loaded entries after them
+    if constexpr (!kOdd) fresh_lines(s, tab);
+    asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3)::"memory");
+    if constexpr (kOdd) philox_rounds<5, 10>(s.ph);
+    else philox_rounds<0, 5>(s.ph);
+    asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3), "+v"(R0.y), "+v"(R1.y), "+v"(R2.y), "+v"(R3.y),
+                      "+v"(C0.y), "+v"(C1.y), "+v"(C2.y), "+v"(C3.y), "+v"(fq), "+v"(gq), "+v"(fp), "+v"(gp));
     *tr.a = (uint8_t)a;
     *tr.p = (int32_t)pts;
-    // line sums of the pre-spawn board; the next board's swap the spawn's row and column entries
-    const uint32_t SRp = f0 + f1 + f2 + f3, SCp = g0 + g1 + g2 + g3;
-    const uint32_t SR = SRp - fp + fq, SC = SCp - gp + gq;
+    // line sums of the next board (bits 16..31 of a sum hold the points / maximum fields' sum, which no
+    // byte select below reads) and of the pre-spawn board
+    const uint32_t SR = R0.y + R1.y + R2.y + R3.y, SC = C0.y + C1.y + C2.y + C3.y;
+    const uint32_t SRp = SR - fq + fp, SCp = SC - gq + gp;
     // #lines that can move per direction in nibbles {UP, DOWN, LEFT, RIGHT} -> legal bits 0..3: a
     // nibble n in 0..4 gets bit 3 set by n + 7; the 24-bit product gathers bits 3, 7, 11, 15 at 12..15
     const uint32_t nl = __builtin_amdgcn_perm(SR, SC, 0x0C0C0501u);
@@ -350,20 +383,26 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     uint32_t sa = stats_bytes(SRp, SCp) | pos_a;
     const uint32_t pos2 = v > Ma ? sp : v == Ma ? min(pos_a, sp) : pos_a;
     uint32_t S = stats_bytes(SR, SC) | pos2 | (max(Ma, v) << 24);
-    if (!kSmall && Ma > 11u) {  // an exponent outside kLine12: the SWAR statistics and legal mask
+    if (!kSmall && Ma > kMaxLineDigit) {  // an exponent outside kLine11: the SWAR statistics and legal mask
         const MonoStats ms = mono_stats(pre);
         sa = pack_stats(ms);
         S = pack_stats(mono_add_tile(ms, pre, sp, v));
         s.legal = legal_mask(moved);
     }
     const uint32_t mono_a = mono_value_packed(sa);
-    // game over: a new game from the pair's spare words (kFresh, prepared with the draw); selects,
-    // so the whole pair stays one basic block
+    // game over: a new game from the pair's spare words (kFresh, prepared with the draw) with the
+    // records of its lines; selects, so the whole pair stays one basic block
     const bool over = s.legal == 0u;
     const uint32_t fl = over ? FLAG_DONE | FLAG_RESET | s.flegal : s.legal;
     s.b = sel4(over, s.fb, s.b);
     s.legal = over ? s.flegal : s.legal;
     s.S = over ? s.fS : S;
+    const uint2 nR[4] = {R0, R1, R2, R3}, nC[4] = {C0, C1, C2, C3};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        s.R[i] = make_uint2(over ? s.fR[i].x : nR[i].x, over ? s.fR[i].y : nR[i].y);
+        s.C[i] = make_uint2(over ? s.fC[i].x : nC[i].x, over ? s.fC[i].y : nC[i].y);
+    }
     *tr.pot = mono_b | (mono_a << 8) | ((uint32_t)s.empt_b << 16) | (empt_a << 24);
     *tr.f = (uint8_t)fl;
     s.empt_b = over ? 14 : (int)empt_a - 1;
@@ -379,16 +418,17 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
 // step: the board the action was taken on [T][N][16], action, points, potentials, flags.
 // Step c (absolute Philox counter) takes word c & 1 of the stream-1 draw at counter c >> 1, so one
 // Philox draw serves two steps (and the reset that may end one of them).  The legal mask is
-// carried from the previous step (the action is always legal); the move goes through the LDS row
-// table while every exponent is <= 11 (the SWAR compute path otherwise); points come from the
-// table.  Workgroups are persistent over boards, so large N keeps several waves per SIMD with one
-// LDS table per CU.
+// carried from the previous step (the action is always legal), and so are the kLine11 records of
+// the board's rows and columns, which hold the move in every direction, its points and the slid
+// lines' maximum: a step's only table reads are the records of the board it produces.  A board
+// holding an exponent > 10 takes the SWAR compute path.  Workgroups are persistent over boards, so
+// large N keeps several waves per SIMD with one LDS table per CU.
 __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ boards, int64_t n, int64_t steps,
                                                            uint4 *__restrict__ tb, uint8_t *__restrict__ ta,
                                                            int32_t *__restrict__ tp, uint32_t *__restrict__ tpot,
                                                            uint8_t *__restrict__ tf, RngArgs rng,
                                                            uint32_t *__restrict__ ticket = nullptr) {
-    // kRow12 then kLine12; every 4-bit-masked index of either table stays inside (kRolloutLdsWords)
+    // kLine11, then kFresh and kFreshLines (the layout and the address bounds are at the top of the file)
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kRolloutLdsWords];
     stage_row_table(s_row);
     const uint64_t ctr0 = rng_counter(rng);
@@ -413,6 +453,8 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         s.D = philox_draw(rng.seed, pair, env, 1u);
         s.ph = philox_start(rng.seed, pair + 1u, env, 1u);
         fresh_prep(s, s_row);
+        refill_lines(s, s_row);
+        if (ctr0 & 1u) fresh_lines(s, s_row);  // an odd first step has no even step before it
         // per-lane record addresses, advanced one row (n elements) per step: no array base in an SGPR
         // pair across the loop (the loop's SGPR spills)
         TrajRows tr{tb + li, ta + li, tp + li, tpot + li, tf + li};
@@ -425,9 +467,11 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
             t = 1;
         }
         for (; t + 2 <= steps; t += 2, pair++) {
-            // every board of the wave <= 2^9 at the pair's start: both steps stay inside the tables
-            // (the move adds at most 1 to the maximum), so the pair runs without the fallback branches
-            if (__all(s.S < (10u << 24))) {
+            // every board of the wave <= 2^8 at the pair's start: both steps stay inside kLine11
+            // (a move adds at most 1 to the maximum), so the pair runs without the fallback branches
+            // and without masking its addresses.  The other pair keeps the carried records valid in
+            // every lane whose board is <= 2^10, so a wave changes between the two freely.
+            if (__all(s.S < (9u << 24))) {
                 rollout_step<false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
                 tr.next(n);
                 rollout_step<true, true>(s, s_row, tr, rng.seed, pair + 2u, env);
@@ -491,7 +535,7 @@ static int rollout_launch(g2048_stream_t stream, int8_t *boards, int64_t n, int6
     if (!boards || !traj_boards || !traj_actions || !traj_points || !traj_pot || !traj_flags || !aligned16(boards) ||
         !aligned16(traj_boards) || ((uintptr_t)traj_pot & 3u) || ((uintptr_t)traj_points & 3u))
         return G2048_EINVAL;
-    // one workgroup per CU holds the 129 KiB LDS tables; its size scales with N up to 1024 threads
+    // one workgroup per CU holds the 149 KiB LDS tables; its size scales with N up to 1024 threads
     // so that large N runs 4 waves per SIMD while N = 65 536 still spreads over all 256 CUs
     int64_t threads = (n + 255) / 256;
     threads = threads < 64 ? 64 : threads > 1024 ? 1024 : ((threads + 63) / 64) * 64;
