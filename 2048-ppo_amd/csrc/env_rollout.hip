@@ -42,10 +42,12 @@ static_assert(8u * lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit
               lut::kFusedEntries * 8u <= kLineLdsBytes, "kLine11 reads stay inside the table");
 static_assert(8u + 1u + 1u <= kMaxLineDigit, "a fast pair (start <= 8) stays inside kLine11");
 static_assert(lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) < 65536u, "column indices fit the packed-u16 sums");
-//  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry above)
+//  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry above), which reset_reload
+//    reads in the lanes whose game ended
 static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line records inside kLine11");
-//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of board, 16 B of line
-//    addresses, 4 B of statistics
+//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of line addresses and 4 B of
+//    statistics in fresh_prep (every lane, once per pair), 16 B of board at kFreshBoardBase + 16 i in
+//    reset_reload (the ending lanes)
 static_assert(60u * 15u + 4u * 14u + 3u == lut::kFreshEntries - 1u, "kFresh index range");
 static_assert(kFreshStatBase + 4u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
 
@@ -215,16 +217,17 @@ struct RolloutLane {
                       // z / w = the words of a reset inside the pair (at most one: a reset board
                       // cannot end again one move later)
     PhiloxState ph;   // draw of the next pair, computed half per step inside the LDS round trip
-    uint4 fb;         // the board a reset inside the current pair starts (D.z, D.w -> kFresh) ...
+    uint32_t fbo;     // the board a reset inside the current pair starts (D.z, D.w -> kFresh): its LDS
+                      // byte address (kFreshBoardBase + 16 i), read only by the lanes whose game ends ...
     uint32_t flegal;  // ... its legal mask and packed statistics
     uint32_t fS;
-    uint4 fla;        // ... the LDS addresses of the kLine11 records of its rows and columns (8 x u16) ...
-    uint2 fR[4], fC[4];  // ... and those records, read one step after the addresses (fresh_lines)
+    uint4 fla;        // ... and the LDS addresses of the kLine11 records of its rows and columns (8 x u16)
 };
 
-// the current pair's auto-reset board from kFresh (fresh_from_pair's board and fresh_stats' results,
-// read once per pair right after the draw is known, long before a step can need them), and the
-// addresses of the records of its eight lines (kFreshLines)
+// the current pair's auto-reset board in kFresh (fresh_from_pair's board and fresh_stats' results):
+// its index, its statistics word and the addresses of the records of its eight lines (kFreshLines),
+// read once per pair right after the draw is known, long before a step can need them.  The board and
+// the eight records are read by reset_reload, in the lanes whose game ends and nowhere else.
 __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__restrict__ tab) {
     const uint32_t a = s.D.z, bw = s.D.w;
     const uint64_t pb = (uint64_t)bw * 15u;  // one v_mad_u64_u32: k2 and the low word
@@ -232,24 +235,30 @@ __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__res
     const uint32_t i = 60u * (a >> 28) + 4u * k2 + ((a << 4) >= kTwoThreshold ? 2u : 0u) +
                        ((uint32_t)pb >= kTwoThreshold ? 1u : 0u);
     const char *t = reinterpret_cast<const char *>(tab);
-    s.fb = *reinterpret_cast<const uint4 *>(t + kFreshBoardBase + 16u * i);
+    s.fbo = kFreshBoardBase + 16u * i;
     s.fla = *reinterpret_cast<const uint4 *>(t + kFreshLineBase + 16u * i);
     const uint32_t st = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
     s.flegal = st >> 28;
     s.fS = st & 0x0FFFFFFFu;
 }
-// ... and the records themselves, one step later: issued with the even step's own table reads, so
-// that the second of the two dependent reads adds no LDS round trip of its own
-__device__ __forceinline__ void fresh_lines(RolloutLane &s, const uint32_t *__restrict__ tab) {
-    const uint4 la = s.fla;
-    s.fR[0] = lds_rec(tab, la.x & 0xFFFFu);
-    s.fR[1] = lds_rec(tab, la.x >> 16);
-    s.fR[2] = lds_rec(tab, la.y & 0xFFFFu);
-    s.fR[3] = lds_rec(tab, la.y >> 16);
-    s.fC[0] = lds_rec(tab, la.z & 0xFFFFu);
-    s.fC[1] = lds_rec(tab, la.z >> 16);
-    s.fC[2] = lds_rec(tab, la.w & 0xFFFFu);
-    s.fC[3] = lds_rec(tab, la.w >> 16);
+// The auto-reset of the lanes whose game ended (called under the divergent `if (over)`): the fresh
+// board and the records of its eight lines, loaded over the step's own b / R / C.  An exec-masked
+// load is a select that costs no VALU: the other lanes keep what the step's round trip loaded, and a
+// wave without an ending skips the block.  The empty asm keeps the address unpack inside the block
+// (the compiler would otherwise hoist the eight ALU operations into every step).
+__device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__restrict__ tab) {
+    uint4 la = s.fla;
+    asm volatile("" : "+v"(la.x), "+v"(la.y), "+v"(la.z), "+v"(la.w));
+    // the board first: the next step stores it before it picks among the records
+    s.b = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(tab) + s.fbo);
+    s.R[0] = lds_rec(tab, la.x & 0xFFFFu);
+    s.R[1] = lds_rec(tab, la.x >> 16);
+    s.R[2] = lds_rec(tab, la.y & 0xFFFFu);
+    s.R[3] = lds_rec(tab, la.y >> 16);
+    s.C[0] = lds_rec(tab, la.z & 0xFFFFu);
+    s.C[1] = lds_rec(tab, la.z >> 16);
+    s.C[2] = lds_rec(tab, la.w & 0xFFFFu);
+    s.C[3] = lds_rec(tab, la.w >> 16);
 }
 
 // the records of the current board's lines from the board itself (launch start; the steps keep them
@@ -362,7 +371,6 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     uint32_t fp = lds_half(tab, rp + 4u), gp = lds_half(tab, cp + 4u);
     // half of the next pair's Philox rounds fill the round trip: the empty asm statements start them
     // after the table loads are issued (memory clobber) and consume the loaded entries after them
-    if constexpr (!kOdd) fresh_lines(s, tab);
     asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3)::"memory");
     if constexpr (kOdd) philox_rounds<5, 10>(s.ph);
     else philox_rounds<0, 5>(s.ph);
@@ -378,34 +386,42 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     // nibble n in 0..4 gets bit 3 set by n + 7; the 24-bit product gathers bits 3, 7, 11, 15 at 12..15
     const uint32_t nl = __builtin_amdgcn_perm(SR, SC, 0x0C0C0501u);
     s.legal = (__umul24((nl + 0x7777u) & 0x8888u, 0x249u) >> 12) & 15u;
+    if (!kSmall && Ma > kMaxLineDigit) s.legal = legal_mask(moved);  // an exponent outside kLine11
+    const bool over = s.legal == 0u;
+    s.R[0] = R0, s.R[1] = R1, s.R[2] = R2, s.R[3] = R3;
+    s.C[0] = C0, s.C[1] = C1, s.C[2] = C2, s.C[3] = C3;
     // statistics before the spawn (the record's mono_a) and after it (carried to the next step): the
     // spawned tile changes the maximum / its first cell only when it reaches the maximum
     uint32_t sa = stats_bytes(SRp, SCp) | pos_a;
     const uint32_t pos2 = v > Ma ? sp : v == Ma ? min(pos_a, sp) : pos_a;
     uint32_t S = stats_bytes(SR, SC) | pos2 | (max(Ma, v) << 24);
-    if (!kSmall && Ma > kMaxLineDigit) {  // an exponent outside kLine11: the SWAR statistics and legal mask
+    if (!kSmall && Ma > kMaxLineDigit) {  // an exponent outside kLine11: the SWAR statistics
         const MonoStats ms = mono_stats(pre);
         sa = pack_stats(ms);
         S = pack_stats(mono_add_tile(ms, pre, sp, v));
-        s.legal = legal_mask(moved);
     }
     const uint32_t mono_a = mono_value_packed(sa);
-    // game over: a new game from the pair's spare words (kFresh, prepared with the draw) with the
-    // records of its lines; selects, so the whole pair stays one basic block
-    const bool over = s.legal == 0u;
-    const uint32_t fl = over ? FLAG_DONE | FLAG_RESET | s.flegal : s.legal;
-    s.b = sel4(over, s.fb, s.b);
-    s.legal = over ? s.flegal : s.legal;
-    s.S = over ? s.fS : S;
-    const uint2 nR[4] = {R0, R1, R2, R3}, nC[4] = {C0, C1, C2, C3};
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        s.R[i] = make_uint2(over ? s.fR[i].x : nR[i].x, over ? s.fR[i].y : nR[i].y);
-        s.C[i] = make_uint2(over ? s.fC[i].x : nC[i].x, over ? s.fC[i].y : nC[i].y);
-    }
     *tr.pot = mono_b | (mono_a << 8) | ((uint32_t)s.empt_b << 16) | (empt_a << 24);
+    uint32_t fl = s.legal;
+    s.S = S;
+    s.empt_b = (int)empt_a - 1;
+    // game over: a new game from the pair's spare words (kFresh, prepared with the draw), in the lanes
+    // that ended only.  The fresh board and the records of its lines are loaded over the step's own
+    // (reset_reload), and its legal mask and statistics -- the word fresh_prep read with the draw, so
+    // no round trip is exposed here -- are moved in: nothing of the reset is computed or selected in
+    // a lane that plays on, and a wave without an ending skips the block.  It sits at the end of the
+    // step (measured faster than right after the legal mask, profiles/r08a): the next step's board
+    // store and record pick are the first to need the loads, after its action arithmetic; in the odd
+    // step the Philox start and fresh_prep follow and cover them, and fresh_prep overwrites fbo / fla /
+    // flegal / fS for the next pair only after this block has used the current pair's.
+    if (over) {
+        reset_reload(s, tab);
+        fl = FLAG_DONE | FLAG_RESET | s.flegal;
+        s.legal = s.flegal;
+        s.S = s.fS;
+        s.empt_b = 14;
+    }
     *tr.f = (uint8_t)fl;
-    s.empt_b = over ? 14 : (int)empt_a - 1;
     if constexpr (kOdd) {
         s.D = make_uint4(s.ph.c0, s.ph.c1, s.ph.c2, s.ph.c3);
         s.ph = philox_start(seed, next_pair, env, 1u);
@@ -454,7 +470,6 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         s.ph = philox_start(rng.seed, pair + 1u, env, 1u);
         fresh_prep(s, s_row);
         refill_lines(s, s_row);
-        if (ctr0 & 1u) fresh_lines(s, s_row);  // an odd first step has no even step before it
         // per-lane record addresses, advanced one row (n elements) per step: no array base in an SGPR
         // pair across the loop (the loop's SGPR spills)
         TrajRows tr{tb + li, ta + li, tp + li, tpot + li, tf + li};

@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""Per-basic-block instruction counts of env_rollout_kernel from its assembly (make asm):
+python3 tools/asm_blocks.py /tmp/env_rollout.s [min_valu]
+
+One line per block: label, VALU, of which v_cndmask, LDS reads, scratch_* instructions,
+v_readlane / v_writelane, s_waitcnt lgkmcnt, and the branch targets, so the inner loop's header, its two
+pair variants, the masked reset blocks and the tail can be read off and summed.
+"""
+import re
+import sys
+
+
+def blocks(path, kernel="env_rollout_kernel"):
+    out, cur, inside = [], None, False
+    for line in open(path):
+        t = line.strip()
+        if not inside:
+            if re.match(r"^_Z\w*%s\w*:" % kernel, t):
+                inside = True
+                cur = {"label": "entry", "ins": []}
+                out.append(cur)
+            continue
+        if t.startswith(".Lfunc_end"):
+            break
+        m = re.match(r"^(\.LBB\d+_\d+):", t)
+        if m:
+            cur = {"label": m.group(1), "ins": []}
+            out.append(cur)
+            continue
+        if not t or t.startswith((";", ".", "//")):
+            continue
+        cur["ins"].append(t.split(";")[0].strip())
+        if t.startswith("s_cbranch"):  # the fall-through of a conditional branch is a block of its own
+            base, _, k = cur["label"].partition("+")
+            cur = {"label": "%s+%d" % (base, int(k or 0) + 1), "ins": []}
+            out.append(cur)
+    return out
+
+
+def main():
+    path = sys.argv[1]
+    min_valu = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    print(f"{'block':<12}{'ins':>6}{'valu':>6}{'cnd':>5}{'lds_rd':>7}{'scr':>5}{'lane':>5}{'lgkm':>5}  branches")
+    for b in blocks(path):
+        ins = b["ins"]
+        op = [i.split()[0] for i in ins]
+        valu = sum(o.startswith("v_") and not o.startswith(("v_readlane", "v_writelane", "v_readfirstlane")) for o in op)
+        cnd = sum(o.startswith("v_cndmask") for o in op)
+        lds = sum(o.startswith("ds_read") or o.startswith("ds_load") for o in op)
+        scr = sum(o.startswith("scratch_") for o in op)
+        lane = sum(o.startswith(("v_readlane", "v_writelane")) for o in op)
+        lgkm = sum(o == "s_waitcnt" and "lgkmcnt" in i for o, i in zip(op, ins))
+        br = [i.split()[0][2:] + "->" + i.split()[-1] for i in ins if i.startswith(("s_cbranch", "s_branch"))]
+        if valu >= min_valu:
+            print(f"{b['label']:<12}{len(ins):>6}{valu:>6}{cnd:>5}{lds:>7}{scr:>5}{lane:>5}{lgkm:>5}  {' '.join(br)}")
+
+
+if __name__ == "__main__":
+    main()
