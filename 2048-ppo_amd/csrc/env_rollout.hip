@@ -1,13 +1,15 @@
 // env_rollout.hip -- the synthetic random-legal rollout (the bench's headline workload,
-// g2048_env_rollout_random / _adv of include/g2048.h): env_rollout_kernel with its LDS tables and
-// per-step helpers, in a translation unit of its own so that it alone is built with the machine
-// scheduler's occupancy bias at 0 (Makefile: one wave per SIMD at the benchmark size, where the issue
-// schedule, not occupancy, sets the step time; the rest of libg2048 keeps the default bias).
+// g2048_env_rollout_random / _adv of include/g2048.h): env_rollout_kernel with its per-step helpers
+// (the LDS tables and their staging are line11_lds.hpp's, shared with mc_search.hip), in a
+// translation unit of its own so that it alone is built with the machine scheduler's occupancy bias
+// at 0 (Makefile: one wave per SIMD at the benchmark size, where the issue schedule, not occupancy,
+// sets the step time; the rest of libg2048 keeps the default bias).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "board.hpp"
 #include "rowtable.hpp"
+#include "line11_lds.hpp"
 #include "step.hpp"
 #include "launch_util.hpp"
 #include "../../include/g2048.h"
@@ -16,32 +18,13 @@ using namespace g2048;
 
 namespace {
 
-__device__ const lut::Line11Table kLine11 __attribute__((aligned(16))) = lut::Line11Table();
-static_assert(lut::line11_table_ok(lut::Line11Table()), "kLine11 fields against slide_entry / line_entry");
-
-// LDS layout of env_rollout_kernel: kLine11 at byte 0 (8-byte records, 115 KiB with its padding),
-// then the auto-reset boards (kFresh), the addresses of their line records (kFreshLines) and their
-// statistics.
-__device__ const lut::FreshTable kFresh __attribute__((aligned(16))) = lut::FreshTable();
-__device__ const lut::FreshLineTable kFreshLines __attribute__((aligned(16))) = lut::FreshLineTable();
-static_assert(lut::fresh_lines_ok(lut::FreshTable(), lut::FreshLineTable()), "kFreshLines against the kFresh boards");
-constexpr uint32_t kLineLdsBytes = lut::kFusedEntriesPadded * 8u;             // 117 760
-constexpr uint32_t kFreshBoardBase = kLineLdsBytes;                           // 15 KiB of boards
-constexpr uint32_t kFreshLineBase = kFreshBoardBase + lut::kFreshEntries * 16u;  // 15 KiB of line addresses
-constexpr uint32_t kFreshStatBase = kFreshLineBase + lut::kFreshEntries * 16u;   // 4 KiB of stats
-constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 4096u) / 4u;          // 152 576 B
-static_assert(kRolloutLdsWords * 4u <= 160u * 1024u, "the tables fit the 160 KiB of LDS");
 // Every LDS address the kernel forms:
 //  - a kLine11 record at 8 idx (8 bytes, or the u16 at + 4) with every digit of the line <= 10.  The
 //    wave-uniform fast pair starts with every exponent <= 8 and a move adds at most 1 to the maximum,
 //    so its two steps index boards of exponents <= 9 and <= 10; every other step zeroes the board it
 //    takes addresses from in the lanes that hold an exponent > 10 (their reads are discarded), and
 //    the spawn's pre-spawn lines are the post-spawn ones minus the spawned digit.
-constexpr uint32_t kMaxLineDigit = lut::kLineBase - 1u;
-static_assert(8u * lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) + 8u <= lut::kFusedEntries * 8u &&
-              lut::kFusedEntries * 8u <= kLineLdsBytes, "kLine11 reads stay inside the table");
 static_assert(8u + 1u + 1u <= kMaxLineDigit, "a fast pair (start <= 8) stays inside kLine11");
-static_assert(lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) < 65536u, "column indices fit the packed-u16 sums");
 //  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry above), which reset_reload
 //    reads in the lanes whose game ended
 static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line records inside kLine11");
@@ -50,50 +33,6 @@ static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line 
 //    reset_reload (the ending lanes)
 static_assert(60u * 15u + 4u * 14u + 3u == lut::kFreshEntries - 1u, "kFresh index range");
 static_assert(kFreshStatBase + 4u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
-
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 as_u16x2(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
-
-// LDS byte addresses (8 idx) of the kLine11 records of a board's four rows (a row read left to
-// right) and four columns (top to bottom), from the rows' digit pairs: A_i = cells (i, 0) and
-// (i, 2), B_i = cells (i, 1) and (i, 3) as u16 halves (the bytes themselves, one v_perm each: every
-// exponent of the board is <= 10).  Rows: two packed-u16 dot products each, weights 8 x 11^j.
-// Columns: column pairs (0, 2) and (1, 3) at once as packed-u16 multiply-adds over the rows; the
-// byte address (up to 117 120) does not fit 16 bits, so the halves hold idx and are scaled after.
-__device__ __forceinline__ void line11_addrs(const uint4 &b, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
-    const u16x2 k02 = {8, 968}, k13 = {88, 10648};
-    const uint32_t w[4] = {b.x, b.y, b.z, b.w};
-    u16x2 A[4], B[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        A[i] = as_u16x2(__builtin_amdgcn_perm(0u, w[i], 0x0C020C00u));
-        B[i] = as_u16x2(__builtin_amdgcn_perm(0u, w[i], 0x0C030C01u));
-        ra[i] = __builtin_amdgcn_udot2(B[i], k13, __builtin_amdgcn_udot2(A[i], k02, 0u, false), false);
-    }
-    const u16x2 c02 = A[0] + A[1] * (u16x2){11, 11} + A[2] * (u16x2){121, 121} + A[3] * (u16x2){1331, 1331};
-    const u16x2 c13 = B[0] + B[1] * (u16x2){11, 11} + B[2] * (u16x2){121, 121} + B[3] * (u16x2){1331, 1331};
-    const uint32_t p02 = __builtin_bit_cast(uint32_t, c02), p13 = __builtin_bit_cast(uint32_t, c13);
-    ca[0] = (p02 & 0xFFFFu) << 3;
-    ca[1] = (p13 & 0xFFFFu) << 3;
-    ca[2] = (p02 >> 16) << 3;
-    ca[3] = (p13 >> 16) << 3;
-}
-__device__ __forceinline__ uint2 lds_rec(const uint32_t *tab, uint32_t addr) {
-    return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(tab) + addr);
-}
-__device__ __forceinline__ uint32_t lds_half(const uint32_t *tab, uint32_t addr) {
-    return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(tab) + addr);
-}
-
-// nibble-packed line (dword 0 of a kLine11 record) -> line dword with one exponent per byte, the
-// start-slid half (bits 0..15) or the end-slid half (bits 16..31) by the lane's selector: nibble j of
-// a half is the low nibble of byte j/2 of e (j even) or of e >> 4 (j odd), so one v_perm over
-// (e >> 4, e) places all four and a mask clears the high nibbles.
-constexpr uint32_t kUnpackStartSel = 0x05010400u;  // bytes {n0, n1, n2, n3}
-constexpr uint32_t kUnpackEndSel = 0x07030602u;    // bytes {n4, n5, n6, n7}
-__device__ __forceinline__ uint32_t unpack_row(uint32_t e, uint32_t sel) {
-    return __builtin_amdgcn_perm(e >> 4, e, sel) & 0x0F0F0F0Fu;
-}
 
 // Packed monotonicity statistics of the rollout kernel, one VGPR per board: bits 0..3 pos (the
 // first row-major cell holding the maximum), 8..11 L, 12..15 R, 16..19 T, 20..23 B (board.hpp
@@ -172,37 +111,6 @@ __device__ __forceinline__ uint32_t fresh_stats(uint32_t p1, uint32_t v1, uint32
     s.M = max(v1, v2);
     s.pos = v1 > v2 ? p1 : v2 > v1 ? p2 : min(p1, p2);
     return legal;
-}
-
-// Copy the tables (kLine11, kFresh, kFreshLines) into LDS by LDS-DMA: each wave instruction moves 1 KiB (16 B per lane)
-// straight from global memory into LDS with no VGPR staging, and every piece of the wave is in
-// flight before the single wait (one L2/MALL round trip per launch instead of one per batch).
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
-__device__ __forceinline__ void stage_row_table(uint32_t *s_row) {
-    constexpr int kLinePieces = (int)(kLineLdsBytes / 1024u);                 // 115 pieces of 1 KiB
-    constexpr int kFreshPieces = (int)(lut::kFreshEntries * 16u / 1024u);     // + 15 boards + 15 line addresses + 4 stats
-    static_assert(kLineLdsBytes % 1024u == 0u && lut::kFreshEntries * 16u % 1024u == 0u, "whole 1 KiB pieces");
-    static_assert(sizeof(kLine11.v) == kLineLdsBytes && sizeof(kFresh.b) == kFreshPieces * 1024 &&
-                  sizeof(kFreshLines.a) == kFreshPieces * 1024 && sizeof(kFresh.st) == 4096, "table sizes");
-    constexpr int kAll = kLinePieces + 2 * kFreshPieces + 4;  // the LDS layout is the pieces in this order
-    static_assert(kAll * 1024 == (int)(kRolloutLdsWords * 4u), "the pieces fill the allocation");
-    const char *src = reinterpret_cast<const char *>(kLine11.v);
-    const char *src2 = reinterpret_cast<const char *>(kFresh.b);
-    const char *src3 = reinterpret_cast<const char *>(kFreshLines.a);
-    const char *src4 = reinterpret_cast<const char *>(kFresh.st);
-    char *dst = reinterpret_cast<char *>(s_row);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (int c = wave; c < kAll; c += nw) {
-        const char *g;
-        if (c < kLinePieces) g = src + 1024 * c;
-        else if (c < kLinePieces + kFreshPieces) g = src2 + 1024 * (c - kLinePieces);
-        else if (c < kLinePieces + 2 * kFreshPieces) g = src3 + 1024 * (c - kLinePieces - kFreshPieces);
-        else g = src4 + 1024 * (c - kLinePieces - 2 * kFreshPieces);
-        __builtin_amdgcn_global_load_lds((glb_void_t *)(g + 16 * lane), (lds_void_t *)(dst + 1024 * c), 16, 0, 0);
-    }
-    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) lgkmcnt(0): this wave's pieces have landed
-    __syncthreads();
 }
 
 // Per-lane state of the rollout carried from step to step.
@@ -444,7 +352,7 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
                                                            int32_t *__restrict__ tp, uint32_t *__restrict__ tpot,
                                                            uint8_t *__restrict__ tf, RngArgs rng,
                                                            uint32_t *__restrict__ ticket = nullptr) {
-    // kLine11, then kFresh and kFreshLines (the layout and the address bounds are at the top of the file)
+    // kLine11, then kFresh and kFreshLines (the layout is line11_lds.hpp's, the address bounds are at the top of the file)
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kRolloutLdsWords];
     stage_row_table(s_row);
     const uint64_t ctr0 = rng_counter(rng);

@@ -1,0 +1,110 @@
+// line11_lds.hpp -- the kLine11 line table in LDS, shared by the kernels that play random-legal 2048
+// out of it (env_rollout.hip's env_rollout_kernel, mc_search.hip's mc_search_kernel): the table
+// objects of the code object, the LDS layout, the LDS-DMA staging and the per-line address / record
+// helpers.  Everything has internal linkage: each translation unit holds its own copy of the tables.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "board.hpp"
+#include "rowtable.hpp"
+
+namespace {
+
+__device__ const g2048::lut::Line11Table kLine11 __attribute__((aligned(16))) = g2048::lut::Line11Table();
+static_assert(g2048::lut::line11_table_ok(g2048::lut::Line11Table()), "kLine11 fields against slide_entry / line_entry");
+
+// LDS layout of env_rollout_kernel: kLine11 at byte 0 (8-byte records, 115 KiB with its padding),
+// then the auto-reset boards (kFresh), the addresses of their line records (kFreshLines) and their
+// statistics.
+__device__ const g2048::lut::FreshTable kFresh __attribute__((aligned(16))) = g2048::lut::FreshTable();
+__device__ const g2048::lut::FreshLineTable kFreshLines __attribute__((aligned(16))) = g2048::lut::FreshLineTable();
+static_assert(g2048::lut::fresh_lines_ok(g2048::lut::FreshTable(), g2048::lut::FreshLineTable()), "kFreshLines against the kFresh boards");
+constexpr uint32_t kLineLdsBytes = g2048::lut::kFusedEntriesPadded * 8u;             // 117 760
+constexpr uint32_t kFreshBoardBase = kLineLdsBytes;                           // 15 KiB of boards
+constexpr uint32_t kFreshLineBase = kFreshBoardBase + g2048::lut::kFreshEntries * 16u;  // 15 KiB of line addresses
+constexpr uint32_t kFreshStatBase = kFreshLineBase + g2048::lut::kFreshEntries * 16u;   // 4 KiB of stats
+constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 4096u) / 4u;          // 152 576 B
+static_assert(kRolloutLdsWords * 4u <= 160u * 1024u, "the tables fit the 160 KiB of LDS");
+// A kLine11 record sits at 8 idx (8 bytes, or the u16 at + 4) with every digit of the line <= 10.
+constexpr uint32_t kMaxLineDigit = g2048::lut::kLineBase - 1u;
+static_assert(8u * g2048::lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) + 8u <= g2048::lut::kFusedEntries * 8u &&
+              g2048::lut::kFusedEntries * 8u <= kLineLdsBytes, "kLine11 reads stay inside the table");
+static_assert(g2048::lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) < 65536u, "column indices fit the packed-u16 sums");
+
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u16x2 as_u16x2(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
+
+// LDS byte addresses (8 idx) of the kLine11 records of a board's four rows (a row read left to
+// right) and four columns (top to bottom), from the rows' digit pairs: A_i = cells (i, 0) and
+// (i, 2), B_i = cells (i, 1) and (i, 3) as u16 halves (the bytes themselves, one v_perm each: every
+// exponent of the board is <= 10).  Rows: two packed-u16 dot products each, weights 8 x 11^j.
+// Columns: column pairs (0, 2) and (1, 3) at once as packed-u16 multiply-adds over the rows; the
+// byte address (up to 117 120) does not fit 16 bits, so the halves hold idx and are scaled after.
+__device__ __forceinline__ void line11_addrs(const uint4 &b, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
+    const u16x2 k02 = {8, 968}, k13 = {88, 10648};
+    const uint32_t w[4] = {b.x, b.y, b.z, b.w};
+    u16x2 A[4], B[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        A[i] = as_u16x2(__builtin_amdgcn_perm(0u, w[i], 0x0C020C00u));
+        B[i] = as_u16x2(__builtin_amdgcn_perm(0u, w[i], 0x0C030C01u));
+        ra[i] = __builtin_amdgcn_udot2(B[i], k13, __builtin_amdgcn_udot2(A[i], k02, 0u, false), false);
+    }
+    const u16x2 c02 = A[0] + A[1] * (u16x2){11, 11} + A[2] * (u16x2){121, 121} + A[3] * (u16x2){1331, 1331};
+    const u16x2 c13 = B[0] + B[1] * (u16x2){11, 11} + B[2] * (u16x2){121, 121} + B[3] * (u16x2){1331, 1331};
+    const uint32_t p02 = __builtin_bit_cast(uint32_t, c02), p13 = __builtin_bit_cast(uint32_t, c13);
+    ca[0] = (p02 & 0xFFFFu) << 3;
+    ca[1] = (p13 & 0xFFFFu) << 3;
+    ca[2] = (p02 >> 16) << 3;
+    ca[3] = (p13 >> 16) << 3;
+}
+__device__ __forceinline__ uint2 lds_rec(const uint32_t *tab, uint32_t addr) {
+    return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(tab) + addr);
+}
+__device__ __forceinline__ uint32_t lds_half(const uint32_t *tab, uint32_t addr) {
+    return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(tab) + addr);
+}
+
+// nibble-packed line (dword 0 of a kLine11 record) -> line dword with one exponent per byte, the
+// start-slid half (bits 0..15) or the end-slid half (bits 16..31) by the lane's selector: nibble j of
+// a half is the low nibble of byte j/2 of e (j even) or of e >> 4 (j odd), so one v_perm over
+// (e >> 4, e) places all four and a mask clears the high nibbles.
+constexpr uint32_t kUnpackStartSel = 0x05010400u;  // bytes {n0, n1, n2, n3}
+constexpr uint32_t kUnpackEndSel = 0x07030602u;    // bytes {n4, n5, n6, n7}
+__device__ __forceinline__ uint32_t unpack_row(uint32_t e, uint32_t sel) {
+    return __builtin_amdgcn_perm(e >> 4, e, sel) & 0x0F0F0F0Fu;
+}
+
+// Copy the tables (kLine11, kFresh, kFreshLines) into LDS by LDS-DMA: each wave instruction moves 1 KiB (16 B per lane)
+// straight from global memory into LDS with no VGPR staging, and every piece of the wave is in
+// flight before the single wait (one L2/MALL round trip per launch instead of one per batch).
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) void glb_void_t;
+__device__ __forceinline__ void stage_row_table(uint32_t *s_row) {
+    constexpr int kLinePieces = (int)(kLineLdsBytes / 1024u);                 // 115 pieces of 1 KiB
+    constexpr int kFreshPieces = (int)(g2048::lut::kFreshEntries * 16u / 1024u);     // + 15 boards + 15 line addresses + 4 stats
+    static_assert(kLineLdsBytes % 1024u == 0u && g2048::lut::kFreshEntries * 16u % 1024u == 0u, "whole 1 KiB pieces");
+    static_assert(sizeof(kLine11.v) == kLineLdsBytes && sizeof(kFresh.b) == kFreshPieces * 1024 &&
+                  sizeof(kFreshLines.a) == kFreshPieces * 1024 && sizeof(kFresh.st) == 4096, "table sizes");
+    constexpr int kAll = kLinePieces + 2 * kFreshPieces + 4;  // the LDS layout is the pieces in this order
+    static_assert(kAll * 1024 == (int)(kRolloutLdsWords * 4u), "the pieces fill the allocation");
+    const char *src = reinterpret_cast<const char *>(kLine11.v);
+    const char *src2 = reinterpret_cast<const char *>(kFresh.b);
+    const char *src3 = reinterpret_cast<const char *>(kFreshLines.a);
+    const char *src4 = reinterpret_cast<const char *>(kFresh.st);
+    char *dst = reinterpret_cast<char *>(s_row);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    for (int c = wave; c < kAll; c += nw) {
+        const char *g;
+        if (c < kLinePieces) g = src + 1024 * c;
+        else if (c < kLinePieces + kFreshPieces) g = src2 + 1024 * (c - kLinePieces);
+        else if (c < kLinePieces + 2 * kFreshPieces) g = src3 + 1024 * (c - kLinePieces - kFreshPieces);
+        else g = src4 + 1024 * (c - kLinePieces - 2 * kFreshPieces);
+        __builtin_amdgcn_global_load_lds((glb_void_t *)(g + 16 * lane), (lds_void_t *)(dst + 1024 * c), 16, 0, 0);
+    }
+    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) lgkmcnt(0): this wave's pieces have landed
+    __syncthreads();
+}
+
+}  // namespace

@@ -24,7 +24,7 @@ RTG_STATE_DOUBLES = 8
 
 EXPORTED = (
     "g2048_mt_state_words", "g2048_mt_seed", "g2048_env_reset", "g2048_env_step", "g2048_env_rollout_random",
-    "g2048_env_rollout_random_adv",
+    "g2048_env_rollout_random_adv", "g2048_mc_search_workspace_bytes", "g2048_mc_search",
     "g2048_preview_points", "g2048_legal_mask",
     "g2048_obs_encode", "g2048_info_deltas", "g2048_sample_actions", "g2048_rtg_prepare", "g2048_reward_rtg_workspace_bytes",
     "g2048_reward_rtg", "g2048_reward_rtg_ex", "g2048_rtg_finalize", "g2048_build_info", "g2048_episode_scan",
@@ -211,6 +211,8 @@ def load(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         "g2048_env_step": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, rp, u32]),
         "g2048_env_rollout_random": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, rp]),
         "g2048_env_rollout_random_adv": (ctypes.c_int, [vp, vp, i64, i64, vp, vp, vp, vp, vp, rp, vp]),
+        "g2048_mc_search_workspace_bytes": (sz, [i64, i64]),
+        "g2048_mc_search": (ctypes.c_int, [vp, vp, i64, i64, i64, rp, vp, vp, vp, vp, vp, sz]),
         "g2048_preview_points": (ctypes.c_int, [vp, vp, vp, i64]),
         "g2048_legal_mask": (ctypes.c_int, [vp, vp, vp, i64]),
         "g2048_obs_encode": (ctypes.c_int, [vp, vp, vp, i32, i64]),
@@ -418,6 +420,29 @@ def env_rollout_random(boards, steps, traj_boards, traj_actions, traj_points, tr
     else:
         _check(load().g2048_env_rollout_random_adv(*args, _dev(ticket, torch.int32, "ticket")),
                "g2048_env_rollout_random_adv")
+
+
+def mc_search_workspace_bytes(n: int, playouts: int) -> int:
+    return int(load().g2048_mc_search_workspace_bytes(int(n), int(playouts)))
+
+
+def mc_search(boards, playouts: int, depth: int, rng: Rng, score_sum, move_sum=None, legal=None, best=None,
+              workspace=None):
+    """Monte-Carlo playout search (g2048_mc_search): boards int8 [n, 16] -> score_sum int64 [n, 4],
+    move_sum int64 [n, 4], legal / best uint8 [n] (the last three optional).  workspace: a uint8 device
+    tensor of mc_search_workspace_bytes(n, playouts) bytes (zero-filled by the call)."""
+    n = boards.shape[0]
+    for t, nm, k in ((score_sum, "score_sum", 4 * n), (move_sum, "move_sum", 4 * n), (legal, "legal", n),
+                     (best, "best", n)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"mc_search: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("mc_search: a workspace of mc_search_workspace_bytes(n, playouts) bytes is required")
+    _check(load().g2048_mc_search(
+        _stream(boards), _dev(boards, torch.int8, "boards"), n, int(playouts), int(depth), ctypes.byref(rng),
+        _dev(score_sum, torch.int64, "score_sum"), _dev(move_sum, torch.int64, "move_sum"),
+        _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel()), "g2048_mc_search")
 
 
 def preview_points(boards, points4):

@@ -354,6 +354,22 @@ def evaluate(model_path: Path = typer.Argument(...), games: int = typer.Option(1
                                                for v in (512, 1024, 2048)))
 
 
+@app.command("play-mc")
+def play_mc(games: int = typer.Option(100, "--games", "-g"),
+            playouts: int = typer.Option(64, "--playouts", help="random playouts per legal move"),
+            depth: int = typer.Option(64, "--depth", help="moves per playout (0: greedy on points)"),
+            max_moves: Optional[int] = typer.Option(None, "--max-moves", help="stop every game after this many moves")):
+    """Play `games` seeded games (game i spawns like random.seed(i), as `evaluate`) with pure
+    Monte-Carlo playout search: the no-network baseline for `evaluate`'s numbers."""
+    from g2048.search import MonteCarloPlayer
+    player = MonteCarloPlayer(playouts, depth, torch.device("cuda", 0))
+    res = player.play_games(games, max_moves, seeds=list(range(games)))
+    s, tiles = res["scores"], res["max_tiles"]
+    typer.echo(f"Eval Results - Max: {max(s):.0f}, Avg: {sum(s) / len(s):.1f}, Median: {sorted(s)[len(s) // 2]:.0f}")
+    typer.echo("Tiles Reached - " + ", ".join(f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%"
+                                               for v in (512, 1024, 2048)))
+
+
 @app.command("export-demo")
 def export_demo_cmd(model_path: Path = typer.Option("checkpoints/best_model.pt", "--model", "-m"),
                     game_path: Optional[Path] = typer.Option(None, "--game", "-g"),

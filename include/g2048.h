@@ -119,6 +119,31 @@ int g2048_env_rollout_random_adv(g2048_stream_t stream, int8_t *boards, int64_t 
                                  uint8_t *traj_actions, int32_t *traj_points, int8_t *traj_pot, uint8_t *traj_flags,
                                  const g2048_rng *rng, uint32_t *ticket);
 
+/* Pure Monte-Carlo playout search on n root boards (no reference counterpart: the search baseline a
+   trained agent's `evaluate` score is compared with).  For every board i and action a, `playouts`
+   (P, 1..4096) random games of at most `depth` (D, 0..65 536) moves are played after the move a, one
+   per lane L = (4 i + a) P + p, p < P, env id rng->env_base + L, c = rng->counter (+ *counter_dev):
+     - the forced move is g2048_env_step with action a on board i: the spawn from Philox stream 0 at
+       counter c.  An illegal a contributes nothing; a board left without a legal move contributes
+       the move's points and no playout step.
+     - the playout is g2048_env_rollout_random's step without its auto-reset: step t takes word
+       (c + t) & 1 of the stream-1 draw at counter (c + t) >> 1 (action = the high word of
+       u x #legal, spawn from the low word), and a lane stops after its first step that ends the
+       game (that step's points count) or after D steps.
+   score_sum [n][4] int64 = the sum over the P lanes of the forced move's points plus the playout's;
+   move_sum [n][4] int64 (nullable) = the playout steps executed; legal [n] (nullable) = bits 0-3 the
+   legal actions of board i; best [n] (nullable) = the legal action of the largest score_sum, the
+   lowest index among equals, 0xFF for a board without a legal move.  score_sum / move_sum are 16-B
+   aligned.  All sums are integers, so the results are bitwise reproducible.  D = 0 is the one-ply
+   greedy-points player.  The call zero-fills score_sum / move_sum and the workspace itself
+   (g2048_mc_search_workspace_bytes(n, playouts) bytes, 4-B aligned: one arrival counter per board).
+   G2048_EINVAL for an rng mode other than Philox, P or D outside their ranges, n x 4 x P >= 2^31 or
+   a workspace that is too small; n = 0 is a no-op; boards [n,16] is only read. */
+size_t g2048_mc_search_workspace_bytes(int64_t n, int64_t playouts);
+int g2048_mc_search(g2048_stream_t stream, const int8_t *boards, int64_t n, int64_t playouts, int64_t depth,
+                    const g2048_rng *rng, int64_t *score_sum, int64_t *move_sum, uint8_t *legal, uint8_t *best,
+                    void *workspace, size_t workspace_bytes);
+
 /* Game2048.preview_move_rewards (game.py:167-184): points4[i] = merge points of UP, DOWN, LEFT,
    RIGHT on board i, 0 for an illegal direction.  points4 is int32 [N][4], 16-B aligned. */
 int g2048_preview_points(g2048_stream_t stream, const int8_t *boards, int32_t *points4, int64_t n);
