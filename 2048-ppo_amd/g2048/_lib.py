@@ -258,6 +258,30 @@ def mc_search(boards, playouts: int, depth: int, rng: Rng, score_sum, move_sum=N
           workspace.numel())
 
 
+def expectimax_workspace_bytes(n: int, depth: int, form: int = EMAX_AUTO) -> int:
+    """0 for arguments g2048_expectimax would refuse."""
+    return int(load().g2048_expectimax_workspace_bytes(int(n), int(depth), int(form)))
+
+
+def expectimax(boards, depth: int, weights, value, leaves=None, legal=None, best=None, workspace=None,
+               form: int = EMAX_AUTO):
+    """Exact expectimax search (g2048_expectimax): boards int8 [n, 16], weights = (w_points, w_mono,
+    w_empt) -> value int64 [n, 4] (-1: illegal), leaves int64 [n, 4], legal / best uint8 [n] (the last
+    three optional).  workspace: a uint8 device tensor of expectimax_workspace_bytes(n, depth, form)
+    bytes (zero-filled by the call)."""
+    n = boards.shape[0]
+    for t, nm, k in ((value, "value", 4 * n), (leaves, "leaves", 4 * n), (legal, "legal", n), (best, "best", n)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"expectimax: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("expectimax: a workspace of expectimax_workspace_bytes(n, depth, form) bytes is required")
+    w_points, w_mono, w_empt = (int(x) for x in weights)
+    _call("g2048_expectimax", _stream(boards), _dev(boards, torch.int8, "boards"), n, int(depth), w_points, w_mono,
+          w_empt, int(form), _dev(value, torch.int64, "value"), _dev(leaves, torch.int64, "leaves"),
+          _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), _dev(workspace, torch.uint8, "workspace"),
+          workspace.numel())
+
+
 def preview_points(boards, points4):
     _call("g2048_preview_points", _stream(boards), _dev(boards, torch.int8, "boards"),
           _dev(points4, torch.int32, "points4"), boards.shape[0])

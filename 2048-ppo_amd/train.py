@@ -341,6 +341,14 @@ def load_checkpoint_model(ck) -> torch.nn.Module:
     return model
 
 
+def _echo_results(res: dict) -> None:
+    """The two result lines of `evaluate`, `play-mc` and `play-expectimax`."""
+    s, tiles = res["scores"], res["max_tiles"]
+    typer.echo(f"Eval Results - Max: {max(s):.0f}, Avg: {sum(s) / len(s):.1f}, Median: {sorted(s)[len(s) // 2]:.0f}")
+    typer.echo("Tiles Reached - " + ", ".join(f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%"
+                                               for v in (512, 1024, 2048)))
+
+
 @app.command()
 def evaluate(model_path: Path = typer.Argument(...), games: int = typer.Option(100, "--games", "-g")):
     """Evaluate a checkpoint on `games` seeded games (game i spawns like random.seed(i))."""
@@ -348,10 +356,7 @@ def evaluate(model_path: Path = typer.Argument(...), games: int = typer.Option(1
     model = load_checkpoint_model(torch.load(model_path, map_location="cpu", weights_only=True))
     dev = torch.device("cuda", 0)
     res = play_games(model.to(dev).eval(), games, None, dev, seeds=list(range(games)), record=False)
-    s, tiles = res["scores"], res["max_tiles"]
-    typer.echo(f"Eval Results - Max: {max(s):.0f}, Avg: {sum(s) / len(s):.1f}, Median: {sorted(s)[len(s) // 2]:.0f}")
-    typer.echo("Tiles Reached - " + ", ".join(f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%"
-                                               for v in (512, 1024, 2048)))
+    _echo_results(res)
 
 
 @app.command("play-mc")
@@ -364,10 +369,22 @@ def play_mc(games: int = typer.Option(100, "--games", "-g"),
     from g2048.search import MonteCarloPlayer
     player = MonteCarloPlayer(playouts, depth, torch.device("cuda", 0))
     res = player.play_games(games, max_moves, seeds=list(range(games)))
-    s, tiles = res["scores"], res["max_tiles"]
-    typer.echo(f"Eval Results - Max: {max(s):.0f}, Avg: {sum(s) / len(s):.1f}, Median: {sorted(s)[len(s) // 2]:.0f}")
-    typer.echo("Tiles Reached - " + ", ".join(f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%"
-                                               for v in (512, 1024, 2048)))
+    _echo_results(res)
+
+
+@app.command("play-expectimax")
+def play_expectimax(games: int = typer.Option(100, "--games", "-g"),
+                    depth: int = typer.Option(3, "--depth", help="moves looked ahead, the root move included (1..4)"),
+                    w_points: int = typer.Option(1, "--w-points", help="integer weight of the merge points (0..4096)"),
+                    w_mono: int = typer.Option(64, "--w-mono", help="integer weight of the leaf's monotonicity"),
+                    w_empt: int = typer.Option(128, "--w-empt", help="integer weight of the leaf's emptiness"),
+                    max_moves: Optional[int] = typer.Option(None, "--max-moves",
+                                                            help="stop every game after this many moves")):
+    """Play `games` seeded games (game i spawns like random.seed(i), as `evaluate`) with exact
+    depth-limited expectimax search: the deterministic no-network baseline beside `play-mc`."""
+    from g2048.search import ExpectimaxPlayer
+    player = ExpectimaxPlayer(depth, (w_points, w_mono, w_empt), torch.device("cuda", 0))
+    _echo_results(player.play_games(games, max_moves, seeds=list(range(games))))
 
 
 @app.command("export-demo")

@@ -144,6 +144,47 @@ int g2048_mc_search(g2048_stream_t stream, const int8_t *boards, int64_t n, int6
                     const g2048_rng *rng, int64_t *score_sum, int64_t *move_sum, uint8_t *legal, uint8_t *best,
                     void *workspace, size_t workspace_bytes);
 
+/* Exact depth-limited expectimax on n root boards (no reference counterpart: the deterministic search
+   baseline beside g2048_mc_search).  It maximises over the four moves and takes the expectation over
+   every spawn: each empty cell, exponent 1 (a 2) with weight 9 and exponent 2 (a 4) with weight 1.
+   All arithmetic is int64 with 16 fractional bits, S = 65 536; the weights w_points / w_mono / w_empt
+   are integers in [0, 4096]; depth d (moves looked ahead, the root move included) is in [1, 4].
+   move(b, a), its merge points pts(b, a) and legality (move(b, a) != b) are g2048_env_step's, mono /
+   empt the potentials it reports, evaluated on a pre-spawn board like mono_after / empt_after:
+     H(s)    = S (w_mono mono(s) + w_empt empt(s))               leaf: an after-state (moved, no spawn)
+     A(s, 0) = H(s)
+     A(s, k) = floor( sum over the empty cells c of s of (9 M(s + 1@c, k) + M(s + 2@c, k))
+                      / (10 E(s)) ),  E(s) = #empty cells of s (>= 1 after a legal move),  k >= 1
+     M(b, k) = max over legal a of (S w_points pts(b, a) + A(move(b, a), k - 1)); 0 without a legal move
+     value[i][a] = S w_points pts(root_i, a) + A(move(root_i, a), d - 1) for a legal a, -1 for an illegal a
+   Every legal value is >= 0, so -1 marks illegality unambiguously and a dead position (0) is the
+   worst outcome.  The sum inside A is exact before its one floor division, so no result depends on
+   the summation order: every output is bitwise reproducible and the same in every form.  Bound: with
+   weights <= 2^12, merge points per move < 2^19 and d <= 4, M < 2^50; a chance node sums at most 320
+   weighted terms (16 cells x (9 + 1)), < 2^59: every intermediate stays far below 2^63.
+   value [n][4] int64 (16-B aligned); leaves [n][4] int64 (nullable, 16-B aligned) = the number of leaf
+   after-states (A(., 0) evaluations) under that root action, 0 for an illegal one; legal [n]
+   (nullable) = bits 0-3 the legal actions of board i; best [n] (nullable) = the legal action of the
+   largest value, the lowest index among equals, 0xFF for a board without a legal move (the conventions
+   of g2048_mc_search).  boards [n,16] is only read.
+   form: NARROW = one lane per (board, action, first spawn), 128 n lanes; WIDE (d >= 2) = one lane per
+   (board, action, first spawn, second action, second spawn), 16 384 n lanes, for a handful of boards;
+   AUTO = WIDE at d = 3 for n < 192 and at d = 4 for n < 2^17 (what was measured faster), else NARROW.
+   The call zero-fills what it accumulates into:
+   the workspace (g2048_expectimax_workspace_bytes(n, depth, form) bytes, 16-B aligned; 0 is returned
+   for arguments the call would refuse).  G2048_EINVAL for depth outside 1..4, a weight outside
+   0..4096, an unknown form, WIDE with depth < 2, n < 0 or a lane count >= 2^31, a null or misaligned
+   boards / value / workspace (or misaligned leaves), or a workspace that is too small; n = 0 is a
+   no-op. */
+#define G2048_EMAX_AUTO 0
+#define G2048_EMAX_NARROW 1
+#define G2048_EMAX_WIDE 2
+size_t g2048_expectimax_workspace_bytes(int64_t n, int64_t depth, int32_t form);
+int g2048_expectimax(g2048_stream_t stream, const int8_t *boards, int64_t n, int64_t depth,
+                     int32_t w_points, int32_t w_mono, int32_t w_empt, int32_t form,
+                     int64_t *value, int64_t *leaves, uint8_t *legal, uint8_t *best,
+                     void *workspace, size_t workspace_bytes);
+
 /* Game2048.preview_move_rewards (game.py:167-184): points4[i] = merge points of UP, DOWN, LEFT,
    RIGHT on board i, 0 for an illegal direction.  points4 is int32 [N][4], 16-B aligned. */
 int g2048_preview_points(g2048_stream_t stream, const int8_t *boards, int32_t *points4, int64_t n);
