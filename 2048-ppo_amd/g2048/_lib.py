@@ -22,7 +22,7 @@ import torch
 
 LIB_PATH = Path(__file__).resolve().parent / "libg2048.so"
 INCLUDE_DIR = Path(__file__).resolve().parents[2] / "include"
-HEADERS = ("g2048.h", "g2048_ppo.h", "g2048_urm.h")  # in this order: a nested struct is known when it is used
+HEADERS = ("g2048.h", "g2048_ntuple.h", "g2048_ppo.h", "g2048_urm.h")  # in this order: a nested struct is known when it is used
 
 
 class G2048Error(RuntimeError):
@@ -33,6 +33,7 @@ class G2048Error(RuntimeError):
 _STRUCT_NAMES = {
     "g2048_rng": "Rng",
     "g2048_reward_cfg": "RewardCfg",
+    "g2048_ntuple_net": "NtNet",
     "g2048_dropout": "Dropout",
     "g2048_policy_rollout_args": "PolicyRolloutArgs",
     "g2048_colsum_job": "ColsumJob",
@@ -280,6 +281,65 @@ def expectimax(boards, depth: int, weights, value, leaves=None, legal=None, best
           w_empt, int(form), _dev(value, torch.int64, "value"), _dev(leaves, torch.int64, "leaves"),
           _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), _dev(workspace, torch.uint8, "workspace"),
           workspace.numel())
+
+
+def make_ntuple_net(cells, weights: torch.Tensor) -> NtNet:
+    """The host struct of an n-tuple network: cells = T tuples of K cell indices (4 row + col), weights the
+    device int32 tensor of its T x 16^K table entries.  Raises for a net the library would refuse."""
+    cells = [[int(c) for c in tup] for tup in cells]
+    T, K = len(cells), len(cells[0]) if cells else 0
+    if not 1 <= T <= NT_MAX_TUPLES or not 1 <= K <= NT_MAX_LEN or any(len(tup) != K for tup in cells):
+        raise G2048Error(f"ntuple: 1..{NT_MAX_TUPLES} tuples of one length in 1..{NT_MAX_LEN}, got {cells}")
+    flat = [c for tup in cells for c in tup]
+    net = NtNet(T, K, (ctypes.c_int32 * (NT_MAX_TUPLES * NT_MAX_LEN))(*flat), _dev(weights, torch.int32, "weights"))
+    count = int(load().g2048_ntuple_weight_count(ctypes.byref(net)))
+    if count == 0:
+        raise G2048Error(f"ntuple: cells {cells} are refused (0..15, distinct within a tuple; weights 16-B aligned)")
+    if weights.numel() != count:
+        raise G2048Error(f"ntuple: weights hold {weights.numel()} elements, the net needs {count}")
+    return net
+
+
+def ntuple_value(net: NtNet, boards, value):
+    """value int64 [n] = V(boards[i]) (g2048_ntuple_value)."""
+    n = boards.shape[0]
+    if value.numel() < n:
+        raise G2048Error(f"ntuple_value: value holds {value.numel()} elements, needs {n}")
+    _call("g2048_ntuple_value", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+          _dev(value, torch.int64, "value"), n)
+
+
+def ntuple_choose(net: NtNet, boards, q=None, legal=None, best=None):
+    """The greedy choice (g2048_ntuple_choose): q int64 [n, 4] (INT64_MIN: illegal), legal / best uint8 [n];
+    each optional, not all three."""
+    n = boards.shape[0]
+    for t, nm, k in ((q, "q", 4 * n), (legal, "legal", n), (best, "best", n)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_choose: {nm} holds {t.numel()} elements, needs {k}")
+    _call("g2048_ntuple_choose", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+          _dev(q, torch.int64, "q"), _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), n)
+
+
+def ntuple_td_workspace_bytes(n: int) -> int:
+    """0 for an n g2048_ntuple_td would refuse."""
+    return int(load().g2048_ntuple_td_workspace_bytes(int(n)))
+
+
+def ntuple_td(net: NtNet, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
+              workspace=None):
+    """`steps` afterstate TD(0) steps of the n envs on one net (g2048_ntuple_td): boards / after int8 [n, 16],
+    pending uint8 [n], run_score int64 [n] carried; stats int64 [4] accumulated (optional); workspace: a
+    uint8 device tensor of ntuple_td_workspace_bytes(n) bytes."""
+    n = boards.shape[0]
+    for t, nm, k in ((after, "after", 16 * n), (pending, "pending", n), (run_score, "run_score", n), (stats, "stats", 4)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_td: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("ntuple_td: a workspace of ntuple_td_workspace_bytes(n) bytes is required")
+    _call("g2048_ntuple_td", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+          _dev(after, torch.int8, "after"), _dev(pending, torch.uint8, "pending"),
+          _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), ctypes.byref(rng),
+          _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
 
 
 def preview_points(boards, points4):

@@ -1,0 +1,150 @@
+"""The n-tuple network trained by afterstate TD(0) (include/g2048_ntuple.h): the table-based 2048
+learner (Szubert & Jaskowski 2014; Yeh et al. 2016), on the device.
+
+NTupleNet: T tuples of K board cells and one int32 table of 16^K weights per tuple; the value of a
+board is the sum of the 8 T weights its tuples index under the 8 symmetries of the square, in points x
+4096.  NTupleTrainer: `envs` games learning in parallel on one net (g2048_ntuple_td): every env plays the
+move of the largest points + value and moves the weights of its previous after-state towards that
+maximum; the updates are integer adds, so a run is reproducible bit for bit.  NTuplePlayer: the greedy
+player of a net (g2048_ntuple_choose) in search.py's game loop.
+"""
+
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from .search import _SearchPlayer
+
+PRESETS = {
+    "lines-squares-4": [[0, 1, 2, 3], [4, 5, 6, 7], [0, 1, 4, 5], [1, 2, 5, 6], [5, 6, 9, 10]],
+    "4x6": [[0, 1, 2, 3, 4, 5], [4, 5, 6, 7, 8, 9], [0, 1, 2, 4, 5, 6], [4, 5, 6, 8, 9, 10]],
+}
+MAX_TUPLES, MAX_LEN, FRAC_BITS = L.NT_MAX_TUPLES, L.NT_MAX_LEN, L.NT_FRAC_BITS
+MAX_ENVS = (1 << 28) - 1
+
+
+def _check_cells(cells) -> list[list[int]]:
+    if isinstance(cells, str):
+        if cells not in PRESETS:
+            raise ValueError(f"unknown tuple preset {cells!r}: one of {sorted(PRESETS)}")
+        cells = PRESETS[cells]
+    cells = [[int(c) for c in tup] for tup in cells]
+    if not 1 <= len(cells) <= MAX_TUPLES:
+        raise ValueError(f"a net has 1..{MAX_TUPLES} tuples, got {len(cells)}")
+    k = len(cells[0])
+    if not 1 <= k <= MAX_LEN or any(len(tup) != k for tup in cells):
+        raise ValueError(f"every tuple has the same 1..{MAX_LEN} cells, got {cells}")
+    for tup in cells:
+        if any(not 0 <= c <= 15 for c in tup) or len(set(tup)) != k:
+            raise ValueError(f"the cells of a tuple are distinct and in 0..15, got {tup}")
+    return cells
+
+
+class NTupleNet:
+    """cells: a preset name or T tuples of K cell indices (4 row + col).  weights: int32 [T, 16^K] on
+    `device`, zero at the start (the greedy-on-points player)."""
+
+    def __init__(self, cells="lines-squares-4", device="cuda", weights: torch.Tensor | None = None):
+        self.cells = _check_cells(cells)
+        self.device = torch.device(device)
+        shape = (len(self.cells), 16 ** len(self.cells[0]))
+        if weights is None:
+            weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        else:
+            if weights.dtype != torch.int32 or tuple(weights.shape) != shape:
+                raise ValueError(f"weights must be int32 {shape}, got {weights.dtype} {tuple(weights.shape)}")
+            weights = weights.to(self.device).contiguous()
+        self.weights = weights
+        self._c = None
+
+    @property
+    def c(self) -> L.NtNet:
+        """The host struct the library reads (the first use needs the device)."""
+        if self._c is None:
+            self._c = L.make_ntuple_net(self.cells, self.weights)
+        return self._c
+
+    def value(self, boards: torch.Tensor) -> torch.Tensor:
+        """V of boards int8 [n, 16] -> int64 [n] (points x 4096)."""
+        out = torch.empty(boards.shape[0], dtype=torch.int64, device=boards.device)
+        L.ntuple_value(self.c, boards, out)
+        return out
+
+    def save(self, path) -> None:
+        torch.save({"cells": self.cells, "weights": self.weights.cpu()}, path)
+
+    @classmethod
+    def load(cls, path, device="cuda") -> "NTupleNet":
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        return cls(ck["cells"], device, ck["weights"])
+
+
+class NTupleTrainer:
+    """`envs` Philox games keyed by `seed`: the reset at counter 0, TD step s at counter 1 + s.
+    lr_shift in 1..30: an update adds delta / 2^lr_shift to each of the 8 T weights; concurrent envs add
+    up on shared weights, so a usable lr_shift grows with envs (10 at 256)."""
+
+    def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048):
+        envs, lr_shift = int(envs), int(lr_shift)
+        if not 1 <= envs <= MAX_ENVS:
+            raise ValueError(f"envs must be in [1, {MAX_ENVS}], got {envs}")
+        if not 1 <= lr_shift <= 30:
+            raise ValueError(f"lr_shift must be in [1, 30], got {lr_shift}")
+        self.net, self.envs, self.lr_shift, self.seed = net, envs, lr_shift, int(seed)
+        self.counter = 0
+        self.boards = None
+
+    def _start(self):
+        d, n = self.net.device, self.envs
+        self.boards = torch.zeros(n, 16, dtype=torch.int8, device=d)
+        self.after = torch.zeros(n, 16, dtype=torch.int8, device=d)
+        self.pending = torch.zeros(n, dtype=torch.uint8, device=d)
+        self.run_score = torch.zeros(n, dtype=torch.int64, device=d)
+        self.stats = torch.zeros(4, dtype=torch.int64, device=d)
+        self.workspace = torch.empty(L.ntuple_td_workspace_bytes(n), dtype=torch.uint8, device=d)
+        L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
+        self.counter = 1
+
+    @torch.no_grad()
+    def train(self, steps: int) -> dict:
+        """`steps` more TD steps of every env -> the statistics of these steps: games finished, their
+        mean and largest score (0 without a finished game) and the updates applied."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps must be positive, got {steps}")
+        if self.boards is None:
+            self._start()
+        self.stats.zero_()
+        L.ntuple_td(self.net.c, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift,
+                    L.make_rng(L.RNG_PHILOX, self.seed, self.counter), self.stats, self.workspace)
+        self.counter += steps
+        games, score_sum, best, updates = self.stats.tolist()
+        return {"games": games, "mean_score": score_sum / games if games else 0.0, "max_score": best,
+                "updates": updates, "score_sum": score_sum}
+
+
+class NTuplePlayer(_SearchPlayer):
+    """Plays the move of the largest points + V(after-state) of `net`; it draws nothing."""
+
+    def __init__(self, net: NTupleNet):
+        if not isinstance(net, NTupleNet):
+            raise ValueError(f"NTuplePlayer needs an NTupleNet, got {type(net).__name__}")
+        self.net = net
+        self.device = net.device
+
+    def _buffers(self, n: int):
+        d = self.device
+        return (torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, 4, dtype=torch.int64, device=d),
+                torch.empty(n, dtype=torch.uint8, device=d))
+
+    def _search(self, boards, move_index: int, bufs):
+        best, q, legal = bufs
+        L.ntuple_choose(self.net.c, boards, q, legal, best)
+
+    def choose(self, boards: torch.Tensor):
+        """boards int8 [n, 16] -> (best uint8 [n] (0xFF: no legal move), q int64 [n, 4] (INT64_MIN:
+        illegal), legal uint8 [n])."""
+        bufs = self._buffers(boards.shape[0])
+        self._search(boards, 0, bufs)
+        return bufs

@@ -342,7 +342,7 @@ def load_checkpoint_model(ck) -> torch.nn.Module:
 
 
 def _echo_results(res: dict) -> None:
-    """The two result lines of `evaluate`, `play-mc` and `play-expectimax`."""
+    """The two result lines of `evaluate`, `play-mc`, `play-expectimax` and `play-ntuple`."""
     s, tiles = res["scores"], res["max_tiles"]
     typer.echo(f"Eval Results - Max: {max(s):.0f}, Avg: {sum(s) / len(s):.1f}, Median: {sorted(s)[len(s) // 2]:.0f}")
     typer.echo("Tiles Reached - " + ", ".join(f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%"
@@ -384,6 +384,53 @@ def play_expectimax(games: int = typer.Option(100, "--games", "-g"),
     depth-limited expectimax search: the deterministic no-network baseline beside `play-mc`."""
     from g2048.search import ExpectimaxPlayer
     player = ExpectimaxPlayer(depth, (w_points, w_mono, w_empt), torch.device("cuda", 0))
+    _echo_results(player.play_games(games, max_moves, seeds=list(range(games))))
+
+
+@app.command("train-ntuple")
+def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD steps of every env"),
+                 envs: int = typer.Option(256, "--envs", help="games learning in parallel on the one net"),
+                 lr_shift: int = typer.Option(10, "--lr-shift", help="an update adds delta / 2^lr_shift (1..30); "
+                                                                    "raise it with --envs"),
+                 tuples: str = typer.Option("lines-squares-4", "--tuples", help="tuple preset: lines-squares-4, 4x6"),
+                 seed: int = typer.Option(0x2048, "--seed"),
+                 out: Optional[Path] = typer.Option(None, "--out", help="where to save the net"),
+                 print_frequency: int = typer.Option(1000, "--print-freq", "-p", help="steps between two reports")):
+    """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
+    reproducible bit for bit.  Prints the games finished and their mean score per interval."""
+    from g2048.ntuple import PRESETS, NTupleNet, NTupleTrainer
+    if tuples not in PRESETS:
+        typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
+        raise typer.Exit(1)
+    if not torch.cuda.is_available():
+        typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
+        raise typer.Exit(1)
+    net = NTupleNet(tuples, torch.device("cuda", 0))
+    tr = NTupleTrainer(net, envs, lr_shift, seed)
+    typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
+               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}")
+    done = 0
+    while done < steps:
+        k = min(max(print_frequency, 1), steps - done)
+        st = tr.train(k)
+        done += k
+        typer.echo(f"step {done}: games {st['games']}, mean score {st['mean_score']:.1f}, max {st['max_score']}, "
+                   f"updates {st['updates']}")
+    if out is not None:
+        out.parent.mkdir(parents=True, exist_ok=True)
+        net.save(out)
+        typer.echo(f"Saved the net to {out}")
+
+
+@app.command("play-ntuple")
+def play_ntuple(model_path: Path = typer.Argument(..., metavar="MODEL", help="a net saved by train-ntuple"),
+                games: int = typer.Option(100, "--games", "-g"),
+                max_moves: Optional[int] = typer.Option(None, "--max-moves",
+                                                        help="stop every game after this many moves")):
+    """Play `games` seeded games (game i spawns like random.seed(i), as `evaluate`) with the greedy
+    player of a trained n-tuple network."""
+    from g2048.ntuple import NTupleNet, NTuplePlayer
+    player = NTuplePlayer(NTupleNet.load(model_path, torch.device("cuda", 0)))
     _echo_results(player.play_games(games, max_moves, seeds=list(range(games))))
 
 

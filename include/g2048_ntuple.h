@@ -1,0 +1,98 @@
+/*
+ * g2048_ntuple.h -- n-tuple network with afterstate TD(0) learning (Szubert & Jaskowski 2014; Yeh et
+ * al. 2016) on the 2048 engine of g2048.h: the table-based learner a 2048 agent is compared with.  No
+ * reference counterpart.  The conventions are those of g2048.h: device pointers (except the host
+ * structs g2048_ntuple_net / g2048_rng, read during the call), asynchronous on `stream`, no allocation
+ * and no host synchronisation (hipGraph-capturable), 0 / G2048_EINVAL (nothing enqueued) / a positive
+ * hipError_t, n = 0 a no-op.  This text is the specification; tests/ntuple_reference.py restates it.
+ *
+ * The network.  T tuples of K cells each (cell = 4 row + col) and one table of 16^K int32 weights per
+ * tuple.  All values are integers: points x S, S = 2^G2048_NT_FRAC_BITS = 4096.
+ *   e(b, c)  = min(b[c], 15)                                   the exponent of cell c, clamped
+ *   idx_t(b) = sum over j < K of e(b, cells[K t + j]) << 4 j
+ *   V(b)     = sum over t < T and over the 8 symmetries g of the square of W_t[idx_t(g(b))]   (int64)
+ * The sum runs over the whole symmetry group (4 rotations x an optional reflection), so it does not
+ * depend on how the eight are enumerated, and V(g(b)) = V(b).  A tuple that a symmetry maps onto
+ * itself reads one weight twice: that is intended, in the value and in the update.
+ *
+ * The choice.  move(b, a), its merge points pts(b, a) and legality (move(b, a) != b) are
+ * g2048_env_step's; move(b, a) is the after-state: moved, before the spawn.
+ *   q[a] = S pts(b, a) + V(move(b, a)) for a legal a, INT64_MIN for an illegal a
+ *   best = the legal action of the largest q, the lowest index among equals, 0xFF without a legal move
+ *   legal = bits 0-3 the legal actions (the conventions of g2048_mc_search)
+ *
+ * The TD step.  Env i at step t < steps uses Philox counter c + t, c = rng->counter (+ *counter_dev).
+ * Every read of a step sees the weights as they were before that step's updates.
+ *   1. the greedy action of boards[i]: with a legal move a* = best, target = q[a*], s' = move(board, a*);
+ *      without one there is no move and target = 0.
+ *   2. if pending[i] != 0:  delta = (pending[i] == 2 ? 0 : target) - V(after[i])
+ *        D = clamp((delta + (1 << (lr_shift - 1))) >> lr_shift, -2^30, 2^30)     arithmetic shift
+ *      and D is added to each of the 8 T weights (counted with multiplicity) that V(after[i]) reads.
+ *      Such an (env, step) counts as one update applied, whatever D is.
+ *   3. the env is stepped: exactly g2048_env_step with the action a* (0 without a legal move) and
+ *      G2048_OPT_AUTO_RESET at counter c + t, env id rng->env_base + i.  run_score[i] += points; on
+ *      G2048_FLAG_DONE the finished score run_score[i] goes into stats and run_score[i] = 0.
+ *   4. with a legal move after[i] = s' and pending[i] = DONE ? 2 : 1; without one pending[i] = 0.
+ * So pending[i] = 0: no after-state is waiting (the start: zero-fill it); 1: after[i] waits for the
+ * value of the next board; 2: after[i] ended its game, its target is 0.
+ * Updates are integer adds, which commute: the weights after a step do not depend on the order in
+ * which the n envs add, and a run is bitwise reproducible.
+ * Range.  The weights WRAP on overflow (two's complement): one weight holds +-2^31 / S = +-2^19
+ * points.  Concurrent envs add up on shared weights, so a usable lr_shift grows with n: from zero
+ * weights, five 4-tuples and n = 256, lr_shift 9 drove weights to 2^31 while lr_shift 10 learned.
+ */
+#ifndef G2048_NTUPLE_H
+#define G2048_NTUPLE_H
+
+#include "g2048.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define G2048_NT_MAX_TUPLES 8
+#define G2048_NT_MAX_LEN 6
+#define G2048_NT_FRAC_BITS 12 /* S = 4096: values are points x S */
+
+typedef struct g2048_ntuple_net { /* host struct, read during the call */
+    int32_t num_tuples;           /* T in 1..8 */
+    int32_t tuple_len;            /* K in 1..6, the same for every tuple */
+    int32_t cells[48];            /* cells[K t + j] = 4 row + col, 0..15; cells within a tuple distinct */
+    int32_t *weights;             /* device int32 [T][16^K], 16-B aligned */
+} g2048_ntuple_net;
+
+/* T x 16^K, the number of int32 weights; 0 for a net the calls below would refuse (a null net, T, K or
+   a cell out of range, a repeated cell in a tuple, null or misaligned weights). */
+size_t g2048_ntuple_weight_count(const g2048_ntuple_net *net);
+
+/* value[i] = V(boards[i]), int64 [n].  boards [n,16] is only read.  0 <= n < 2^31.
+   G2048_EINVAL for a net g2048_ntuple_weight_count refuses, n out of range, null or misaligned
+   boards, a null value. */
+int g2048_ntuple_value(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *value,
+                       int64_t n);
+
+/* The choice on n boards: q int64 [n][4] (16-B aligned), legal / best uint8 [n]; each of the three is
+   nullable, but not all three at once.  boards [n,16] is only read.  0 <= n < 2^31.  G2048_EINVAL as
+   g2048_ntuple_value, for a misaligned q and for three null outputs. */
+int g2048_ntuple_choose(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *q,
+                        uint8_t *legal, uint8_t *best, int64_t n);
+
+/* `steps` TD steps of n envs learning in parallel on one net, two launches per step (evaluate, then
+   update and step; stream order between them is the read-before-write rule).  boards / after [n,16]
+   int8 (16-B aligned), pending uint8 [n], run_score int64 [n] are read at the start and carried:
+   a second call continues the first when the counter is advanced by `steps`.  stats (nullable) int64
+   [4] = {games finished, sum of their scores, largest finished score, updates applied}: accumulated,
+   not zeroed (the largest by maximum).  workspace: g2048_ntuple_td_workspace_bytes(n) bytes, 16-B
+   aligned, contents ignored and overwritten (0 is returned for an n the call would refuse).
+   G2048_EINVAL for a net g2048_ntuple_weight_count refuses, steps < 1, lr_shift outside 1..30, n < 0 or
+   n >= 2^28, an rng mode other than Philox (or a misaligned counter_dev), null or misaligned boards /
+   after, a null pending / run_score, a null, misaligned or too small workspace. */
+size_t g2048_ntuple_td_workspace_bytes(int64_t n);
+int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
+                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* G2048_NTUPLE_H */
