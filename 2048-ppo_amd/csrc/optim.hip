@@ -101,19 +101,31 @@ struct AdamGroup {
 struct AdamArgs {
     AdamGroup g[kAdamMaxGroups];
     int count;
-    float b1, b2, eps, wd;
+    float eps, wd;
+    // from the caller's double betas (torch.optim.AdamW keeps them so), each rounded to fp32 ONCE on the
+    // host: 1 - (float)0.999 is 1.3e-5 below 0.001, a bias of every exp_avg_sq, and 1 - powf(b2, t) lost up
+    // to 6e-5 at small t to the same cancellation -- the bias corrections are -expm1(t ln beta) instead
+    float b2;          // (float)beta2
+    float omb1, omb2;  // (float)(1 - beta1), (float)(1 - beta2)
+    float lnb1, lnb2;  // (float)ln beta1, (float)ln beta2
     const float *lr;
     const float *step;
     const float *clip;
 };
 
+// the bias corrections of step count t: 1 - b1^t and sqrt(1 - b2^t)
+__device__ __forceinline__ void adamw_bias(const AdamArgs &a, float t, float &bc1, float &bc2s) {
+    bc1 = -expm1f(t * a.lnb1);
+    bc2s = sqrtf(-expm1f(t * a.lnb2));
+}
+
 // one AdamW update of element i (torch.optim.AdamW: decoupled decay, bias corrections)
-__device__ __forceinline__ void adamw_elem(const AdamGroup &gr, int64_t i, float lr, float coef, float b1, float b2,
-                                           float eps, float wd, float bc1, float bc2s) {
+__device__ __forceinline__ void adamw_elem(const AdamGroup &gr, int64_t i, float lr, float coef, float omb1, float b2,
+                                           float omb2, float eps, float wd, float bc1, float bc2s) {
     const float g = gr.grad[i] * coef;
     float p = gr.param[i] * (1.0f - lr * wd);
-    const float m = gr.m[i] + (1.0f - b1) * (g - gr.m[i]);
-    const float v = gr.v[i] * b2 + (1.0f - b2) * g * g;
+    const float m = gr.m[i] + omb1 * (g - gr.m[i]);
+    const float v = gr.v[i] * b2 + omb2 * g * g;
     gr.m[i] = m;
     gr.v[i] = v;
     p -= (lr / bc1) * m / (sqrtf(v) / bc2s + eps);
@@ -1193,13 +1205,13 @@ __device__ __forceinline__ void adam_blocks(const MuonArgs &args, int b, int nb)
         cf = clip_coef(args.max_norm, sqrtf(t));
     }
     const AdamArgs &a = args.adam;
-    const float t = *a.step;
-    const float bc1 = 1.0f - powf(a.b1, t), bc2s = sqrtf(1.0f - powf(a.b2, t));
+    float bc1, bc2s;
+    adamw_bias(a, *a.step, bc1, bc2s);
     for (int k = 0; k < a.count; k++) {
         const AdamGroup gr = a.g[k];
         const float lr = a.lr[gr.lr_index];
         for (int64_t i = (int64_t)b * blockDim.x + threadIdx.x; i < gr.n; i += (int64_t)nb * blockDim.x)
-            adamw_elem(gr, i, lr, cf, a.b1, a.b2, a.eps, a.wd, bc1, bc2s);
+            adamw_elem(gr, i, lr, cf, a.omb1, a.b2, a.omb2, a.eps, a.wd, bc1, bc2s);
     }
 }
 
@@ -1493,15 +1505,14 @@ __global__ __launch_bounds__(kMuonThreads) void muon_kernel(MuonArgs args) {
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
-    const float t = *a.step;
-    const float bc1 = 1.0f - powf(a.b1, t);
-    const float bc2s = sqrtf(1.0f - powf(a.b2, t));
+    float bc1, bc2s;
+    adamw_bias(a, *a.step, bc1, bc2s);
     const float coef = a.clip ? *a.clip : 1.0f;
     for (int k = 0; k < a.count; k++) {
         const AdamGroup gr = a.g[k];
         const float lr = a.lr[gr.lr_index];
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < gr.n; i += (int64_t)gridDim.x * 256)
-            adamw_elem(gr, i, lr, coef, a.b1, a.b2, a.eps, a.wd, bc1, bc2s);
+            adamw_elem(gr, i, lr, coef, a.omb1, a.b2, a.omb2, a.eps, a.wd, bc1, bc2s);
     }
 }
 
@@ -1577,7 +1588,7 @@ static int muon_launch(g2048_stream_t stream, const g2048_muon_matrix *mats, int
                        const float *clip_coef_dev, const float *partials, float max_norm, float *norm_out,
                        float *coef_out, const g2048_muon_cfg *cfg, const AdamArgs *adam = nullptr);
 static int adam_args(const g2048_adamw_group *groups, int32_t count, const float *lr_dev, const float *step_dev,
-                     const float *clip_coef_dev, float beta1, float beta2, float eps, float weight_decay, AdamArgs &a,
+                     const float *clip_coef_dev, double beta1, double beta2, float eps, float weight_decay, AdamArgs &a,
                      int64_t &nmax);
 
 int g2048_muon_step(g2048_stream_t stream, const g2048_muon_matrix *mats, int32_t count, const float *lr_dev,
@@ -1602,7 +1613,7 @@ int g2048_grad_sumsq_tick(g2048_stream_t stream, const float *grad, int64_t n, f
 int g2048_muon_adamw_step_clip(g2048_stream_t stream, const g2048_muon_matrix *mats, int32_t count,
                                const g2048_adamw_group *groups, int32_t ngroups, const float *lr_dev,
                                const float *step_dev, const float *partials, float max_norm, float *norm_out,
-                               float *coef_out, const g2048_muon_cfg *cfg, float beta1, float beta2, float eps,
+                               float *coef_out, const g2048_muon_cfg *cfg, double beta1, double beta2, float eps,
                                float adam_weight_decay) {
     if (!partials || !norm_out || !coef_out || ngroups < 0) return G2048_EINVAL;
     AdamArgs a{};
@@ -1737,7 +1748,7 @@ static int muon_launch(g2048_stream_t stream, const g2048_muon_matrix *mats, int
 }
 
 static int adam_args(const g2048_adamw_group *groups, int32_t count, const float *lr_dev, const float *step_dev,
-                     const float *clip_coef_dev, float beta1, float beta2, float eps, float weight_decay, AdamArgs &a,
+                     const float *clip_coef_dev, double beta1, double beta2, float eps, float weight_decay, AdamArgs &a,
                      int64_t &nmax) {
     if (!groups || count <= 0 || count > kAdamMaxGroups || !lr_dev || !step_dev) return G2048_EINVAL;
     nmax = 0;
@@ -1748,8 +1759,12 @@ static int adam_args(const g2048_adamw_group *groups, int32_t count, const float
         nmax = g.n > nmax ? g.n : nmax;
     }
     a.count = count;
-    a.b1 = beta1;
-    a.b2 = beta2;
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return G2048_EINVAL;
+    a.b2 = (float)beta2;
+    a.omb1 = (float)(1.0 - beta1);
+    a.omb2 = (float)(1.0 - beta2);
+    a.lnb1 = (float)log(beta1);  // beta 0: -inf, and -expm1(-inf) = 1
+    a.lnb2 = (float)log(beta2);
     a.eps = eps;
     a.wd = weight_decay;
     a.lr = lr_dev;
@@ -1759,7 +1774,7 @@ static int adam_args(const g2048_adamw_group *groups, int32_t count, const float
 }
 
 int g2048_adamw_step(g2048_stream_t stream, const g2048_adamw_group *groups, int32_t count, const float *lr_dev,
-                     const float *step_dev, const float *clip_coef_dev, float beta1, float beta2, float eps,
+                     const float *step_dev, const float *clip_coef_dev, double beta1, double beta2, float eps,
                      float weight_decay) {
     AdamArgs a{};
     int64_t nmax = 0;

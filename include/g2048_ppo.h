@@ -464,9 +464,11 @@ typedef struct g2048_adamw_group {
     int32_t pad_;
 } g2048_adamw_group;
 
-/* AdamW step of up to 4 groups; *step_dev is the (already incremented) step count. */
+/* AdamW step of up to 4 groups; *step_dev is the (already incremented) step count.  The betas are
+ * doubles in [0, 1), as torch.optim.AdamW holds them: 1 - beta is rounded to fp32 once (1 - (float)0.999
+ * is 1.3e-5 below 0.001) and the bias corrections 1 - beta^t are -expm1(t ln beta). */
 int g2048_adamw_step(g2048_stream_t stream, const g2048_adamw_group *groups, int32_t count, const float *lr_dev,
-                     const float *step_dev, const float *clip_coef_dev, float beta1, float beta2, float eps,
+                     const float *step_dev, const float *clip_coef_dev, double beta1, double beta2, float eps,
                      float weight_decay);
 
 /* The whole clipped optimizer step in two launches: g2048_grad_sumsq_tick = g2048_grad_sumsq plus
@@ -478,7 +480,7 @@ int g2048_grad_sumsq_tick(g2048_stream_t stream, const float *grad, int64_t n, f
 int g2048_muon_adamw_step_clip(g2048_stream_t stream, const g2048_muon_matrix *mats, int32_t count,
                                const g2048_adamw_group *groups, int32_t ngroups, const float *lr_dev,
                                const float *step_dev, const float *partials, float max_norm, float *norm_out,
-                               float *coef_out, const g2048_muon_cfg *cfg, float beta1, float beta2, float eps,
+                               float *coef_out, const g2048_muon_cfg *cfg, double beta1, double beta2, float eps,
                                float adam_weight_decay);
 
 /* Test hook: the dropout keep mask (uint8 [m,h], 1 = kept) g2048_ln_act_fwd applies. */

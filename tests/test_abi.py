@@ -110,14 +110,14 @@ def test_signatures_spot_checks():
     from g2048 import _lib
     lib = _lib.load()
     vp, i64, i32, u32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
-    sz, f32, P = ctypes.c_size_t, ctypes.c_float, ctypes.POINTER
+    sz, f32, f64, P = ctypes.c_size_t, ctypes.c_float, ctypes.c_double, ctypes.POINTER
     rp, jp = P(_lib.Rng), P(_lib.ColsumJob)
     expected = {
         "g2048_env_step": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, rp, u32]),
         "g2048_mc_search": (ctypes.c_int, [vp, vp, i64, i64, i64, rp, vp, vp, vp, vp, vp, sz]),
         "g2048_ppo_backward": (ctypes.c_int, [vp, P(_lib.MlpBackArgs), P(vp), P(vp), jp]),
         "g2048_muon_adamw_step_clip": (ctypes.c_int, [vp, P(_lib.MuonMatrix), i32, P(_lib.AdamWGroup), i32, vp, vp, vp,
-                                                      f32, vp, vp, P(_lib.MuonCfg), f32, f32, f32, f32]),
+                                                      f32, vp, vp, P(_lib.MuonCfg), f64, f64, f32, f32]),
         "g2048_urm_forward_drop": (ctypes.c_int, [vp, P(_lib.UrmWeights), vp, i32, vp, vp, i64, f32, u64, vp]),
         "g2048_reward_rtg_workspace_bytes": (sz, [i64]),
         "g2048_build_info": (ctypes.c_char_p, []),
