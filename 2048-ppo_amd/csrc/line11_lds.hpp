@@ -1,5 +1,6 @@
 // line11_lds.hpp -- the kLine11 line table in LDS, shared by the kernels that play random-legal 2048
-// out of it (env_rollout.hip's env_rollout_kernel, mc_search.hip's mc_search_kernel): the table
+// out of it (env_rollout.hip's env_rollout_kernel, mc_search.hip's mc_search_kernel, through the step
+// they share in rollout_step.hpp): the table
 // objects of the code object, the LDS layout, the LDS-DMA staging and the per-line address / record
 // helpers.  Everything has internal linkage: each translation unit holds its own copy of the tables.
 #pragma once

@@ -302,8 +302,7 @@ int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *
     NtArgs a;
     if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
-    if (!rng || rng->mode != G2048_RNG_PHILOX || (rng->counter_dev && ((uintptr_t)rng->counter_dev & 7u)))
-        return G2048_EINVAL;
+    if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
     if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
         ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||

@@ -1,0 +1,310 @@
+// rollout_step.hpp -- the one random-legal env step played out of the kLine11 LDS table
+// (line11_lds.hpp), shared by env_rollout.hip's env_rollout_kernel (kTraj = true: the step writes its
+// trajectory record, carries the potentials' statistics and restarts a finished game) and
+// mc_search.hip's mc_search_kernel (kTraj = false: the step only sums points and counts moves, and a
+// finished game stays finished): the lane state carried from step to step, the packed monotonicity
+// statistics, the auto-reset helpers and rollout_step itself.  Both kernels sit at the register
+// ceiling of a 1024-thread block, so the step is one statement sequence with `if constexpr (kTraj)`
+// around what has an effect only in the record; cutting it into helper functions changes the
+// register allocation of both (Monte-Carlo playout search).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "board.hpp"
+#include "rowtable.hpp"
+#include "line11_lds.hpp"
+#include "step.hpp"
+
+namespace {
+
+using namespace g2048;
+
+// Every LDS address a step forms:
+//  - a kLine11 record at 8 idx (8 bytes, or the u16 at + 4) with every digit of the line <= 10.  The
+//    wave-uniform fast pair starts with every exponent <= 8 and a move adds at most 1 to the maximum,
+//    so its two steps index boards of exponents <= 9 and <= 10; every other step, and refill_lines,
+//    zeroes the board it takes addresses from in the lanes that hold an exponent > 10 (their reads are
+//    discarded: those lanes move on the SWAR path), and the spawn's pre-spawn lines are the post-spawn
+//    ones minus the spawned digit.
+constexpr uint32_t kFastPairMax = 8u;  // a pair runs with kSmall when every board's maximum is <= this
+static_assert(kFastPairMax + 1u + 1u <= kMaxLineDigit, "a fast pair (start <= 8) stays inside kLine11");
+//  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry by fresh_lines_ok), which
+//    reset_reload reads in the lanes whose game ended
+static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line records inside kLine11");
+//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of line addresses and 4 B of
+//    statistics in fresh_prep (every lane, once per pair), 16 B of board at kFreshBoardBase + 16 i in
+//    reset_reload (the ending lanes)
+static_assert(60u * 15u + 4u * 14u + 3u == lut::kFreshEntries - 1u, "kFresh index range");
+static_assert(kFreshStatBase + 4u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
+
+// Packed monotonicity statistics, one VGPR per board (step.hpp carry_pack): bits 0..3 pos (the first
+// row-major cell holding the maximum), 8..11 L, 12..15 R, 16..19 T, 20..23 B (board.hpp MonoStats),
+// 24..27 M.  Bytes 1 and 2 are the low bytes of a board's kLine11 row / column line-entry sums.
+// board.hpp mono_value on the packed word: (L, T) and (R, B) as u16 pairs (L, R scaled by 256),
+// one packed max and one dot product give 256 (max(L, R) + max(T, B)); x2 for a corner maximum
+// (>> 7), floor(/2) otherwise (>> 9).  The bit-field extract reads its offset from bits 0..4 of S.
+__device__ __forceinline__ uint32_t mono_value_packed(uint32_t S) {
+    const u16x2 m = __builtin_elementwise_max(as_u16x2(S & 0x000F0F00u), as_u16x2((S >> 4) & 0x000F0F00u));
+    const uint32_t best256 = __builtin_amdgcn_udot2(m, (u16x2){1, 256}, 0u, false);
+    const uint32_t corner = __builtin_amdgcn_ubfe(0x9009u, S, 1u);
+    return best256 >> (9u - 2u * corner);
+}
+// L|R and T|B bytes of a board's kLine11 row sum SR and column sum SC into bytes 1 and 2
+__device__ __forceinline__ uint32_t stats_bytes(uint32_t SR, uint32_t SC) {
+    return __builtin_amdgcn_perm(SC, SR, 0x0C04000Cu);
+}
+
+// Per-lane state carried from step to step.  A kernel sets and reads the members of its kind of
+// step only; the others never exist (a local struct is split into its members).  The member order
+// is part of env_rollout_kernel's register allocation: keep it.
+struct RolloutLane {
+    uint4 b;          // current board (kTraj: never finished between steps)
+    uint32_t legal;   // its legal mask (!kTraj: 0 = the playout is over)
+    uint32_t M;       // !kTraj: its largest exponent (guards the table: > 10 moves on the SWAR path)
+    uint32_t S;       // kTraj: its packed monotonicity statistics (carry_pack); bits 24.. guard the table
+    int empt_b;       // kTraj: its empty-cell count
+    uint2 R[4], C[4]; // the kLine11 records of its rows and columns (valid while its maximum is <= 10;
+                      // a board above that moves on the SWAR path, which does not read them)
+    uint4 D;          // Philox draw of the current pair of steps: x / y = the two steps' words,
+                      // z / w = the words of a reset inside the pair (at most one: a reset board
+                      // cannot end again one move later; !kTraj: unused)
+    PhiloxState ph;   // draw of the next pair, computed half per step inside the LDS round trip
+    // kTraj only:
+    uint32_t fbo;     // the board a reset inside the current pair starts (D.z, D.w -> kFresh): its LDS
+                      // byte address (kFreshBoardBase + 16 i), read only by the lanes whose game ends ...
+    uint32_t flegal;  // ... its legal mask and packed statistics
+    uint32_t fS;
+    uint4 fla;        // ... and the LDS addresses of the kLine11 records of its rows and columns (8 x u16)
+    // !kTraj only:
+    uint32_t score;   // points so far
+    uint32_t moves;   // steps executed
+};
+
+// the current pair's auto-reset board in kFresh (fresh_from_pair's board and fresh_stats' results):
+// its index, its statistics word and the addresses of the records of its eight lines (kFreshLines),
+// read once per pair right after the draw is known, long before a step can need them.  The board and
+// the eight records are read by reset_reload, in the lanes whose game ends and nowhere else.
+__device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__restrict__ tab) {
+    const uint32_t a = s.D.z, bw = s.D.w;
+    const uint64_t pb = (uint64_t)bw * 15u;  // one v_mad_u64_u32: k2 and the low word
+    const uint32_t k2 = (uint32_t)(pb >> 32);
+    const uint32_t i = 60u * (a >> 28) + 4u * k2 + ((a << 4) >= kTwoThreshold ? 2u : 0u) +
+                       ((uint32_t)pb >= kTwoThreshold ? 1u : 0u);
+    const char *t = reinterpret_cast<const char *>(tab);
+    s.fbo = kFreshBoardBase + 16u * i;
+    s.fla = *reinterpret_cast<const uint4 *>(t + kFreshLineBase + 16u * i);
+    const uint32_t st = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
+    s.flegal = st >> 28;
+    s.fS = st & 0x0FFFFFFFu;
+}
+// The auto-reset of the lanes whose game ended (called under the divergent `if (over)`): the fresh
+// board and the records of its eight lines, loaded over the step's own b / R / C.  An exec-masked
+// load is a select that costs no VALU: the other lanes keep what the step's round trip loaded, and a
+// wave without an ending skips the block.  The empty asm keeps the address unpack inside the block
+// (the compiler would otherwise hoist the eight ALU operations into every step).
+__device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__restrict__ tab) {
+    uint4 la = s.fla;
+    asm volatile("" : "+v"(la.x), "+v"(la.y), "+v"(la.z), "+v"(la.w));
+    // the board first: the next step stores it before it picks among the records
+    s.b = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(tab) + s.fbo);
+    s.R[0] = lds_rec(tab, la.x & 0xFFFFu);
+    s.R[1] = lds_rec(tab, la.x >> 16);
+    s.R[2] = lds_rec(tab, la.y & 0xFFFFu);
+    s.R[3] = lds_rec(tab, la.y >> 16);
+    s.C[0] = lds_rec(tab, la.z & 0xFFFFu);
+    s.C[1] = lds_rec(tab, la.z >> 16);
+    s.C[2] = lds_rec(tab, la.w & 0xFFFFu);
+    s.C[3] = lds_rec(tab, la.w >> 16);
+}
+
+// the records of the current board's lines from the board itself (launch start; the steps keep them
+// up to date from then on).  A lane whose board holds an exponent > 10 (mx = its maximum) reads the
+// empty line's.
+__device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__restrict__ tab, uint32_t mx) {
+    const uint4 ab = sel4(mx > kMaxLineDigit, make_uint4(0u, 0u, 0u, 0u), s.b);
+    uint32_t ra[4], ca[4];
+    line11_addrs(ab, ra, ca);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        s.R[i] = lds_rec(tab, ra[i]);
+        s.C[i] = lds_rec(tab, ca[i]);
+    }
+}
+
+struct TrajRows {  // this lane's element of row t of each time-major trajectory array (advanced by n per step)
+    uint4 *b;
+    uint8_t *a;
+    int32_t *p;
+    uint32_t *pot;
+    uint8_t *f;
+    __device__ __forceinline__ void next(int64_t n) {
+        b += n;
+        a += n;
+        p += n;
+        pot += n;
+        f += n;
+    }
+};
+
+// One env step of the synthetic random-legal policy (oracle or_step_word; kTraj: + auto-reset).
+// kOdd = the second step of the pair; kSmall = every board of the wave is inside the table for this
+// step (no SWAR fallback, no address masking).  One 32-bit word u per step: action
+// k = floor(u * nlegal / 2^32); the low word r of that product (uniform given k) picks the spawn cell
+// and value.  kTraj = false never touches tr.
+template <bool kOdd, bool kSmall, bool kTraj>
+__device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__restrict__ tab, const TrajRows &tr,
+                                             uint64_t seed, uint64_t next_pair, uint32_t env) {
+    if constexpr (kTraj) *tr.b = s.b;
+    const uint32_t u = kOdd ? s.D.y : s.D.x;
+    const uint64_t pa = (uint64_t)u * (uint32_t)__popc(s.legal);
+    const uint32_t a = kth_bit4(s.legal, (uint32_t)(pa >> 32)), r = (uint32_t)pa;
+    // the move from the carried records: the columns' for UP / DOWN, the rows' otherwise; the
+    // start-slid half for UP / LEFT, the end-slid one for DOWN / RIGHT (the unpack selector).  No
+    // table read and no address arithmetic: the previous step read these records.
+    const bool vert = a < 2u, rev = (a & 1u) != 0u;
+    const uint32_t usel = rev ? kUnpackEndSel : kUnpackStartSel;
+    const uint32_t e0 = vert ? s.C[0].x : s.R[0].x, e1 = vert ? s.C[1].x : s.R[1].x;
+    const uint32_t e2 = vert ? s.C[2].x : s.R[2].x, e3 = vert ? s.C[3].x : s.R[3].x;
+    const uint32_t h0 = vert ? s.C[0].y : s.R[0].y, h1 = vert ? s.C[1].y : s.R[1].y;
+    const uint32_t h2 = vert ? s.C[2].y : s.R[2].y, h3 = vert ? s.C[3].y : s.R[3].y;
+    const uint32_t mono_b = kTraj ? mono_value_packed(s.S) : 0u;
+    const uint4 w = make_uint4(unpack_row(e0, usel), unpack_row(e1, usel), unpack_row(e2, usel), unpack_row(e3, usel));
+    uint4 moved = sel4(vert, transpose(w), w);
+    // merge points / 4 in bits 16..27 of each record's dword 1, the slid line's maximum in bits 28..31
+    uint32_t pts = (((h0 >> 16) & 0xFFFu) + ((h1 >> 16) & 0xFFFu) + ((h2 >> 16) & 0xFFFu) + ((h3 >> 16) & 0xFFFu)) << 2;
+    uint32_t Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(h0), as_u16x2(h1)),
+                                                                         __builtin_elementwise_max(as_u16x2(h2), as_u16x2(h3)))) >> 28;
+    if (!kSmall && (kTraj ? s.S >> 24 : s.M) > kMaxLineDigit) {  // an exponent outside the table: the SWAR compute path
+        uint32_t mx;
+        moved = apply_move(s.b, a, pts, mx);
+        Ma = board_max(moved);
+    }
+    const uint32_t rm[4] = {moved.x, moved.y, moved.z, moved.w};
+    const uint32_t Zm[4] = {zm(moved.x), zm(moved.y), zm(moved.z), zm(moved.w)};
+    // the first cell of the maximum, for the statistics.  Unlike the other arithmetic that only the
+    // record needs, it has to be switched off by hand: first_cell_eq's v_ffbl_b32 is written-out asm,
+    // which stays in the IR up to instruction selection when unused and moves the schedule of the
+    // kTraj = false step (119 instead of 117 VGPRs, + 0.8 % on the search: profiles/r09a/time_mc_search_ab.log)
+    const uint32_t pos_a = kTraj ? first_cell_eq(rm, Ma) : 0u;
+    // spawn on the k-th empty cell (row-major), k = floor(r * empties / 2^32), value 1 if the low
+    // word of r * empties is below 0.9 * 2^32 (given k that low word is uniform to within
+    // empties / 2^32); the row from the prefix counts of empties, the column inside the row likewise
+    const uint32_t n0 = __popc(Zm[0]), n01 = __popc(Zm[1]) + n0, n012 = __popc(Zm[2]) + n01;
+    const uint32_t empt_a = __popc(Zm[3]) + n012;
+    const uint64_t prod = (uint64_t)r * empt_a;
+    const uint32_t k = (uint32_t)(prod >> 32);
+    const uint32_t v = (uint32_t)prod < kTwoThreshold ? 1u : 2u;
+    const bool r1 = k >= n0, r2 = k >= n01, r3 = k >= n012;  // spawn row >= 1, >= 2, == 3
+    const uint32_t kr = k - (r3 ? n012 : r2 ? n01 : r1 ? n0 : 0u);
+    const uint32_t z = r3 ? Zm[3] : r2 ? Zm[2] : r1 ? Zm[1] : Zm[0];
+    const uint32_t b0 = (z >> 7) & 1u, b01 = b0 + ((z >> 15) & 1u), b012 = b01 + ((z >> 23) & 1u);
+    const bool c1 = kr >= b0, c2 = kr >= b01, c3 = kr >= b012;  // spawn column >= 1, >= 2, == 3
+    const uint32_t row = (uint32_t)r1 + (uint32_t)r2 + (uint32_t)r3, col = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
+    const uint32_t sp = 4u * row + col;
+    const uint4 pre = moved;
+    const uint32_t bits = v << (8u * col);
+    moved.x |= r1 ? 0u : bits;
+    moved.y |= (r1 && !r2) ? bits : 0u;
+    moved.z |= (r2 && !r3) ? bits : 0u;
+    moved.w |= r3 ? bits : 0u;
+    s.b = moved;  // the next board (after the spawn)
+    // The step's one LDS round trip: the records of the next board's four rows and four columns (the
+    // next move, whatever its direction, and this board's line sums), and (kTraj) the line entries of
+    // the spawn's row and column before and after the spawn (dword 1's low half), whose difference
+    // takes the sums back to the moved board's.  The pre-spawn address is the post-spawn one minus
+    // v x 8 x 11^(column / row).  Outside the fast pair a lane holding an exponent > 10 takes its
+    // addresses from an empty board (its reads are discarded below).
+    uint4 ab = moved;
+    uint32_t va = v;
+    if (!kSmall) {
+        const bool big = Ma > kMaxLineDigit;
+        ab = sel4(big, make_uint4(0u, 0u, 0u, 0u), moved);
+        va = big ? 0u : v;
+    }
+    uint32_t ra[4], ca[4];
+    line11_addrs(ab, ra, ca);
+    constexpr uint64_t kW11 = 0x299803C800580008ull;  // 8 x {1, 11, 121, 1331}
+    const uint32_t rq = r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0], cq = c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];
+    const uint32_t rp = rq - va * ((uint32_t)(kW11 >> (16u * col)) & 0xFFFFu);
+    const uint32_t cp = cq - va * ((uint32_t)(kW11 >> (16u * row)) & 0xFFFFu);
+    uint2 R0 = lds_rec(tab, ra[0]), R1 = lds_rec(tab, ra[1]), R2 = lds_rec(tab, ra[2]), R3 = lds_rec(tab, ra[3]);
+    uint2 C0 = lds_rec(tab, ca[0]), C1 = lds_rec(tab, ca[1]), C2 = lds_rec(tab, ca[2]), C3 = lds_rec(tab, ca[3]);
+    uint32_t fq = 0u, gq = 0u, fp = 0u, gp = 0u;
+    if constexpr (kTraj) {
+        fq = lds_half(tab, rq + 4u), gq = lds_half(tab, cq + 4u);
+        fp = lds_half(tab, rp + 4u), gp = lds_half(tab, cp + 4u);
+    }
+    // half of the next pair's Philox rounds fill the round trip: the empty asm statements start them
+    // after the table loads are issued (memory clobber) and consume the loaded entries after them
+    asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3)::"memory");
+    if constexpr (kOdd) philox_rounds<5, 10>(s.ph);
+    else philox_rounds<0, 5>(s.ph);
+    if constexpr (kTraj)
+        asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3), "+v"(R0.y), "+v"(R1.y), "+v"(R2.y), "+v"(R3.y),
+                          "+v"(C0.y), "+v"(C1.y), "+v"(C2.y), "+v"(C3.y), "+v"(fq), "+v"(gq), "+v"(fp), "+v"(gp));
+    else
+        asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3), "+v"(R0.y), "+v"(R1.y), "+v"(R2.y), "+v"(R3.y),
+                          "+v"(C0.y), "+v"(C1.y), "+v"(C2.y), "+v"(C3.y));
+    if constexpr (kTraj) {
+        *tr.a = (uint8_t)a;
+        *tr.p = (int32_t)pts;
+    }
+    // line sums of the next board (bits 16..31 of a sum hold the points / maximum fields' sum, which no
+    // byte select below reads) and of the pre-spawn board
+    const uint32_t SR = R0.y + R1.y + R2.y + R3.y, SC = C0.y + C1.y + C2.y + C3.y;
+    const uint32_t SRp = SR - fq + fp, SCp = SC - gq + gp;
+    // #lines that can move per direction in nibbles {UP, DOWN, LEFT, RIGHT} -> legal bits 0..3: a
+    // nibble n in 0..4 gets bit 3 set by n + 7; the 24-bit product gathers bits 3, 7, 11, 15 at 12..15
+    const uint32_t nl = __builtin_amdgcn_perm(SR, SC, 0x0C0C0501u);
+    s.legal = (__umul24((nl + 0x7777u) & 0x8888u, 0x249u) >> 12) & 15u;
+    if (!kSmall && Ma > kMaxLineDigit) s.legal = legal_mask(moved);  // an exponent outside kLine11
+    const bool over = s.legal == 0u;
+    s.R[0] = R0, s.R[1] = R1, s.R[2] = R2, s.R[3] = R3;
+    s.C[0] = C0, s.C[1] = C1, s.C[2] = C2, s.C[3] = C3;
+    if constexpr (kTraj) {
+        // statistics before the spawn (the record's mono_a) and after it (carried to the next step): the
+        // spawned tile changes the maximum / its first cell only when it reaches the maximum
+        uint32_t sa = stats_bytes(SRp, SCp) | pos_a;
+        const uint32_t pos2 = v > Ma ? sp : v == Ma ? min(pos_a, sp) : pos_a;
+        uint32_t S = stats_bytes(SR, SC) | pos2 | (max(Ma, v) << 24);
+        if (!kSmall && Ma > kMaxLineDigit) {  // an exponent outside kLine11: the SWAR statistics
+            const MonoStats ms = mono_stats(pre);
+            sa = carry_pack(ms);
+            S = carry_pack(mono_add_tile(ms, pre, sp, v));
+        }
+        const uint32_t mono_a = mono_value_packed(sa);
+        *tr.pot = mono_b | (mono_a << 8) | ((uint32_t)s.empt_b << 16) | (empt_a << 24);
+        uint32_t fl = s.legal;
+        s.S = S;
+        s.empt_b = (int)empt_a - 1;
+        // game over: a new game from the pair's spare words (kFresh, prepared with the draw), in the lanes
+        // that ended only.  The fresh board and the records of its lines are loaded over the step's own
+        // (reset_reload), and its legal mask and statistics -- the word fresh_prep read with the draw, so
+        // no round trip is exposed here -- are moved in: nothing of the reset is computed or selected in
+        // a lane that plays on, and a wave without an ending skips the block.  It sits at the end of the
+        // step (measured faster than right after the legal mask, profiles/r08a): the next step's board
+        // store and record pick are the first to need the loads, after its action arithmetic; in the odd
+        // step the Philox start and fresh_prep follow and cover them, and fresh_prep overwrites fbo / fla /
+        // flegal / fS for the next pair only after this block has used the current pair's.
+        if (over) {
+            reset_reload(s, tab);
+            fl = FLAG_DONE | FLAG_RESET | s.flegal;
+            s.legal = s.flegal;
+            s.S = s.fS;
+            s.empt_b = 14;
+        }
+        *tr.f = (uint8_t)fl;
+    } else {  // the finished game stays (legal == 0 ends the playout); only the table guard is carried
+        s.M = max(Ma, v);
+        s.score += pts;
+        s.moves += 1u;
+    }
+    if constexpr (kOdd) {
+        s.D = make_uint4(s.ph.c0, s.ph.c1, s.ph.c2, s.ph.c3);
+        s.ph = philox_start(seed, next_pair, env, 1u);
+        if constexpr (kTraj) fresh_prep(s, tab);
+    }
+}
+
+}  // namespace

@@ -135,7 +135,8 @@ __device__ __forceinline__ StepResult step_board(uint4 &b, bool has_action, uint
 // (round 5) instead of recomputed from the board: the post-spawn board's statistics come from the
 // pre-spawn board's (computed anyway for mono_a) by mono_add_tile -- env_rollout_kernel's rule --,
 // its emptiness is empt_a - 1, and a reset board's are computed afresh.  The carry is one packed
-// word (bits 0..3 pos, 8..11 L, 12..15 R, 16..19 T, 20..23 B, 24..31 M) and the emptiness.
+// word (bits 0..3 pos, 8..11 L, 12..15 R, 16..19 T, 20..23 B, 24..31 M; also the statistics word of
+// rollout_step.hpp's lanes) and the emptiness.
 __device__ __forceinline__ uint32_t carry_pack(const MonoStats &s) {
     return s.pos | ((uint32_t)s.L << 8) | ((uint32_t)s.R << 12) | ((uint32_t)s.T << 16) | ((uint32_t)s.B << 20) |
            (s.M << 24);

@@ -8,8 +8,10 @@ from conftest import golden
 from oracle import oracle as O
 
 
-def mc_ref_lanes(boards, P, D, seed, ctr, env_base=0):
-    """Per lane L = (4 i + a) P + p: (points, playout moves, invalid forced move, alive after it)."""
+def mc_ref_lanes(boards, P, D, seed, ctr, env_base=0, stepped_max=False):
+    """Per lane L = (4 i + a) P + p: (points, playout moves, invalid forced move, alive after it);
+    with stepped_max also [D, lanes]: the largest exponent of the board the lane steps at playout step
+    t, -1 where it steps none (an invalid forced move, or its playout is over)."""
     boards = np.ascontiguousarray(np.asarray(boards, np.int8).reshape(-1, 16))
     n = len(boards)
     rep = np.repeat(boards, 4 * P, axis=0)
@@ -18,13 +20,17 @@ def mc_ref_lanes(boards, P, D, seed, ctr, env_base=0):
     invalid = f["invalid"].astype(bool)
     alive = (O.legal_mask(b1) != 0) & ~invalid
     if D == 0:
-        return np.where(invalid, 0, f["points"]).astype(np.int64), np.zeros(len(rep), np.int64), invalid, alive
+        res = (np.where(invalid, 0, f["points"]).astype(np.int64), np.zeros(len(rep), np.int64), invalid, alive)
+        return res + (np.zeros((0, len(rep)), np.int64),) if stepped_max else res
     _, rec = O.random_rollout_record(b1.copy(), D, seed, step0=ctr, env_base=env_base)
     done = (rec["flags"] & 0x80) != 0
     first = np.where(done.any(0), done.argmax(0), D - 1)
     m = (np.arange(D)[:, None] <= first[None, :]) & alive[None, :]
     pts = np.where(invalid, 0, f["points"] + (rec["points"].astype(np.int64) * m).sum(0))
-    return pts.astype(np.int64), m.sum(0).astype(np.int64), invalid, alive
+    res = (pts.astype(np.int64), m.sum(0).astype(np.int64), invalid, alive)
+    if stepped_max:
+        res += (np.where(m, rec["boards"].reshape(D, len(rep), 16).max(2).astype(np.int64), -1),)
+    return res
 
 
 def mc_ref(boards, P, D, seed, ctr, env_base=0):

@@ -119,6 +119,41 @@ def test_small_groups(dev, n, P):
         assert_equal(Search(dev, boards, P, 16).run(ctr, 3), mc_ref(boards, P, 16, SEED, ctr, 3))
 
 
+def boundary_roots(m):
+    """8 boards of maximum exactly m with two adjacent m's (test_gpu_env_carry.test_table_boundary's)."""
+    rng = np.random.default_rng(200 + m)
+    b = rng.integers(1, m, size=(8, 16)).astype(np.int8)
+    b[rng.random(b.shape) < 0.25] = 0
+    pos = np.random.default_rng(m).integers(0, 3, 8)
+    for i in range(8):
+        if i % 2 == 0:  # a horizontal pair in row i % 4
+            r, c = i % 4, pos[i]
+            b[i, 4 * r + c] = b[i, 4 * r + c + 1] = m
+        else:  # a vertical pair in column i % 4
+            c, r = i % 4, pos[i]
+            b[i, 4 * r + c] = b[i, 4 * r + 4 + c] = m
+    assert (b.max(axis=1) == m).all()
+    return b
+
+
+@pytest.mark.parametrize("ctr", [4, 5])
+@pytest.mark.parametrize("m", [8, 9, 10])
+def test_table_boundary(dev, m, ctr):
+    """Playouts that create m + 1 while they run -- past the fast-pair bound (9: the wave leaves the
+    fast pair), at the top table digit (10) and outside the table (11: the SWAR path) -- in waves
+    (P = 64: one per (board, action)) where other lanes never do: the playout step's own carry of the
+    maximum decides each lane's path."""
+    P, D, env_base = 64, 8, 7
+    boards = boundary_roots(m)
+    pts, moves, invalid, _, mx = mc_ref_lanes(boards, P, D, SEED, ctr, env_base, stepped_max=True)
+    grew = (mx == m + 1).any(axis=0).reshape(-1, 64)  # per wave and lane: it steps a board holding m + 1
+    played = (mx >= 0).any(axis=0).reshape(-1, 64)
+    assert grew.any()
+    assert (grew.any(axis=1) & (played & ~grew).any(axis=1)).any()  # a wave of both kinds of lane
+    ref = pts.reshape(8, 4, P).sum(2), moves.reshape(8, 4, P).sum(2), invalid.reshape(8, 4, P)[:, :, 0]
+    assert_equal(Search(dev, boards, P, D).run(ctr, env_base), ref)
+
+
 def test_same_sums_from_existing_kernels(dev):
     """The device's own g2048_env_step + g2048_env_rollout_random + a torch reduction
     (tools/time_mc_search.py composed_sums) give the kernel's sums."""
