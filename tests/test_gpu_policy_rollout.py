@@ -11,10 +11,9 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from policy_rollout_util import FIELDS, _assert_same, _model, _run
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("boards", "flags", "actions", "logp", "entropy", "value", "points", "max_tile", "pot")
 
 
 @pytest.fixture(scope="module")
@@ -22,39 +21,6 @@ def dev():
     if not torch.cuda.is_available():
         pytest.fail("no ROCm device visible")
     return torch.device("cuda:0")
-
-
-def _model(dev, h, seed):
-    import agent
-    torch.manual_seed(seed)
-    m = agent.GameMLP(agent.MLPConfig(hidden_dim=h, num_layers=2)).to(dev)
-    with torch.no_grad():  # non-trivial heads and LayerNorm affines (the trainer zeroes the heads)
-        for p in m.parameters():
-            p.add_(torch.randn_like(p) * 0.05)
-        m.action_head.weight.mul_(20.0)
-    return m.eval()
-
-
-def _run(dev, m, n, T, fused, episodic=False, seed=9, chunks=None, env_base=0):
-    from g2048.rollout import FusedPolicy, Rollout
-    pol = FusedPolicy(m)
-    ro = Rollout(n, T, dev, seed=seed, env_base=env_base, episodic=episodic)
-    ro.use_fused = fused
-    assert ro.fused(pol) == fused
-    ro.reset()
-    for t0, t1 in chunks or [(0, T)]:
-        ro.steps(t0, t1, pol)
-    torch.cuda.synchronize()
-    return {k: getattr(ro.buf, k).clone() for k in FIELDS}
-
-
-def _assert_same(a, b):
-    for k in FIELDS:
-        x, y = a[k], b[k]
-        if x.dtype.is_floating_point:  # bitwise, -inf included
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        bad = (x != y).reshape(x.shape[0], x.shape[1], -1).any(-1)
-        assert not bool(bad.any()), (k, int(bad.sum()), torch.nonzero(bad)[:5].tolist())
 
 
 @pytest.mark.parametrize("h,n,T,episodic", [(196, 4099, 24, False), (196, 1000, 40, True), (192, 2048, 16, False),
