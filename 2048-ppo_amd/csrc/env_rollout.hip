@@ -122,15 +122,19 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         // per-lane record addresses, advanced one row (n elements) per step: no array base in an SGPR
         // pair across the loop (the loop's SGPR spills)
         TrajRows tr{tb + li, ta + li, tp + li, tpot + li, tf + li};
-        int64_t t = 0;
-        if ((ctr0 & 1u) && steps > 0) {  // the launch starts on the second step of a pair
+        uint64_t left = (uint64_t)steps;  // steps still to run
+        if ((ctr0 & 1u) && left > 0u) {  // the launch starts on the second step of a pair
             philox_rounds<0, 5>(s.ph);
             rollout_step<true, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
             tr.next(n);
             pair++;
-            t = 1;
+            left--;
         }
-        for (; t + 2 <= steps; t += 2, pair++) {
+        // The pair loop counts down to zero.  A 64-bit `t + 2 <= steps` has no scalar compare: it was a
+        // v_mov_b64 + v_cmp_le_i64 feeding the back edge's s_cbranch_vccz plus two 64-bit scalar adds
+        // per pair; `!= 0` is one s_cmp_lg_u64 (-6 instructions per pair, -2.3 % per launch: DESIGN.md
+        // section 6, round 11)
+        for (uint64_t pairs = left >> 1; pairs != 0u; pairs--, pair++) {
             // every board of the wave <= 2^8 at the pair's start: both steps stay inside kLine11
             // (a move adds at most 1 to the maximum), so the pair runs without the fallback branches
             // and without masking its addresses.  The other pair keeps the carried records valid in
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
             }
             tr.next(n);
         }
-        if (t < steps) rollout_step<false, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+        if (left & 1u) rollout_step<false, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
         boards[i] = s.b;
     }
     if (ticket) {

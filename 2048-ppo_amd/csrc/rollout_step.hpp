@@ -73,8 +73,7 @@ struct RolloutLane {
     // kTraj only:
     uint32_t fbo;     // the board a reset inside the current pair starts (D.z, D.w -> kFresh): its LDS
                       // byte address (kFreshBoardBase + 16 i), read only by the lanes whose game ends ...
-    uint32_t flegal;  // ... its legal mask and packed statistics
-    uint32_t fS;
+    uint32_t fst;     // ... its kFresh statistics word, as loaded: legal mask in bits 28..31, packed statistics below
     uint4 fla;        // ... and the LDS addresses of the kLine11 records of its rows and columns (8 x u16)
     // !kTraj only:
     uint32_t score;   // points so far
@@ -94,9 +93,9 @@ __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__res
     const char *t = reinterpret_cast<const char *>(tab);
     s.fbo = kFreshBoardBase + 16u * i;
     s.fla = *reinterpret_cast<const uint4 *>(t + kFreshLineBase + 16u * i);
-    const uint32_t st = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
-    s.flegal = st >> 28;
-    s.fS = st & 0x0FFFFFFFu;
+    // kept as loaded: splitting it here would stop the wave at this load once per pair, and nothing
+    // needs the two fields before a game ends (reset_reload's caller splits it, in the ending lanes)
+    s.fst = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
 }
 // The auto-reset of the lanes whose game ended (called under the divergent `if (over)`): the fresh
 // board and the records of its eight lines, loaded over the step's own b / R / C.  An exec-masked
@@ -281,17 +280,22 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
         // game over: a new game from the pair's spare words (kFresh, prepared with the draw), in the lanes
         // that ended only.  The fresh board and the records of its lines are loaded over the step's own
         // (reset_reload), and its legal mask and statistics -- the word fresh_prep read with the draw, so
-        // no round trip is exposed here -- are moved in: nothing of the reset is computed or selected in
-        // a lane that plays on, and a wave without an ending skips the block.  It sits at the end of the
-        // step (measured faster than right after the legal mask, profiles/r08a): the next step's board
-        // store and record pick are the first to need the loads, after its action arithmetic; in the odd
-        // step the Philox start and fresh_prep follow and cover them, and fresh_prep overwrites fbo / fla /
-        // flegal / fS for the next pair only after this block has used the current pair's.
+        // no round trip is exposed here, split here -- are moved in: nothing of the reset is computed or
+        // selected in a lane that plays on, and a wave without an ending skips the block.  It sits at the
+        // end of the step (measured faster than right after the legal mask, profiles/r08a): the next
+        // step's board store and record pick are the first to need the loads, after its action
+        // arithmetic.  In the odd step fresh_prep follows and overwrites fbo / fla / fst for the next pair
+        // only after this block has used the current pair's.  Nothing covers the loads there: the loop
+        // tail issues fresh_prep's two reads and branches back without a wait, and the loop header (the
+        // next pair's record pick) waits first for the reload's records (lgkmcnt(2): LDS returns in
+        // order, fresh_prep's two reads may stay in flight), 23 instructions after the back edge.
         if (over) {
             reset_reload(s, tab);
-            fl = FLAG_DONE | FLAG_RESET | s.flegal;
-            s.legal = s.flegal;
-            s.S = s.fS;
+            uint32_t st = s.fst;
+            asm volatile("" : "+v"(st));  // the split stays inside the block, like reset_reload's unpack
+            s.legal = st >> 28;
+            s.S = st & 0x0FFFFFFFu;
+            fl = FLAG_DONE | FLAG_RESET | s.legal;
             s.empt_b = 14;
         }
         *tr.f = (uint8_t)fl;
