@@ -192,11 +192,13 @@ __device__ __forceinline__ void row_loss(const float z[5], const RowIn &in, cons
     float se = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; k++) se += (legal >> k) & 1u ? expf(mk[k] - mx) : 0.0f;
-    const float lse = mx + logf(se);
+    // log_softmax as torch forms it, (x - max) - log(sum): adding the max back first (x - (max + log sum))
+    // would round the log-probabilities at the logits' magnitude instead of their own
+    const float lse = logf(se);
     float sm[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) sm[k] = (legal >> k) & 1u ? expf(mk[k] - lse) : 0.0f;
-    const float lp_a = mk[act] - lse;
+    for (int k = 0; k < 4; k++) sm[k] = (legal >> k) & 1u ? expf((mk[k] - mx) - lse) : 0.0f;
+    const float lp_a = (mk[act] - mx) - lse;
     const float olp_a = act == 0 ? in.olp[0] : act == 1 ? in.olp[1] : act == 2 ? in.olp[2] : in.olp[3];
     const float dlt = lp_a - olp_a;
     const float ratio = expf(fminf(fmaxf(dlt, -20.0f), 20.0f));
@@ -223,11 +225,11 @@ __device__ __forceinline__ void row_loss(const float z[5], const RowIn &in, cons
     float se2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; k++) se2 += expf(ck[k] - cmx);
-    const float lse2 = cmx + logf(se2);
+    const float lse2 = logf(se2);
     float lp2[4], p2[4], ent = 0.0f, S = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        lp2[k] = ck[k] - lse2;
+        lp2[k] = (ck[k] - cmx) - lse2;
         p2[k] = expf(lp2[k]);
         if ((legal >> k) & 1u) {
             ent -= p2[k] * lp2[k];
@@ -271,12 +273,12 @@ __device__ __forceinline__ float kl_row(const float o[4], const float z[4]) {
         so += ok[k] ? expf(o[k] - mo) : 0.0f;
         sn += ok[k] ? expf(nz[k] - mn) : 0.0f;
     }
-    const float lso = mo + logf(so), lsn = mn + logf(sn);
+    const float lso = logf(so), lsn = logf(sn);  // (x - max) - log(sum), as in row_loss
     float kl = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (!ok[k]) continue;
-        const float lo = o[k] - lso, ln = nz[k] - lsn;
+        const float lo = (o[k] - mo) - lso, ln = (nz[k] - mn) - lsn;
         kl += expf(lo) * (lo - ln);
     }
     return kl;

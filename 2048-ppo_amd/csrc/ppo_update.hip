@@ -646,29 +646,10 @@ __global__ __launch_bounds__(kThreads) void head_kl_kernel(const uint16_t *__res
         if (r < mv) {
             const float4 o4 = *reinterpret_cast<const float4 *>(old_masked + r * 4);
             const float o[4] = {o4.x, o4.y, o4.z, o4.w};
-            bool valid[4];
-            float mo = -INFINITY, mn = -INFINITY, nz[4];
+            float nz[4];
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                valid[k] = o[k] != -INFINITY;
-                nz[k] = valid[k] ? zs[wave][lane][k] + bias[k] : -INFINITY;
-                mo = fmaxf(mo, o[k]);
-                mn = fmaxf(mn, nz[k]);
-            }
-            float so = 0.0f, sn = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                so += valid[k] ? expf(o[k] - mo) : 0.0f;
-                sn += valid[k] ? expf(nz[k] - mn) : 0.0f;
-            }
-            const float lso = mo + logf(so), lsn = mn + logf(sn);
-            float kl = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (!valid[k]) continue;
-                const float lo = o[k] - lso, ln = nz[k] - lsn;
-                kl += expf(lo) * (lo - ln);
-            }
+            for (int k = 0; k < 4; k++) nz[k] = zs[wave][lane][k] + bias[k];
+            const float kl = kl_row(o, nz);
             ksum += kl;
             kmax = fmaxf(kmax, kl);
         }
@@ -1269,29 +1250,7 @@ __global__ __launch_bounds__(kMwThreads) void mlp_fwd_wide_kernel(const uint16_t
             if (g == 0 && m < mv) {
                 const float4 o4 = *reinterpret_cast<const float4 *>(ka.old_masked + m * 4);
                 const float o[4] = {o4.x, o4.y, o4.z, o4.w};
-                bool ok4[4];
-                float mo = -INFINITY, mn = -INFINITY, nz[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    ok4[k] = o[k] != -INFINITY;
-                    nz[k] = ok4[k] ? z[k] : -INFINITY;
-                    mo = fmaxf(mo, o[k]);
-                    mn = fmaxf(mn, nz[k]);
-                }
-                float so = 0.0f, sn = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    so += ok4[k] ? expf(o[k] - mo) : 0.0f;
-                    sn += ok4[k] ? expf(nz[k] - mn) : 0.0f;
-                }
-                const float lso = mo + logf(so), lsn = mn + logf(sn);
-                float kl = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if (!ok4[k]) continue;
-                    const float lo = o[k] - lso, ln = nz[k] - lsn;
-                    kl += expf(lo) * (lo - ln);
-                }
+                const float kl = kl_row(o, z);
                 ksum += kl;
                 kmax = fmaxf(kmax, kl);
             }
