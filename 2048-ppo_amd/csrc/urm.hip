@@ -1614,9 +1614,9 @@ __global__ __launch_bounds__(256) void urm_rms_res_bwd_kernel(const float *__res
 }
 
 // Training-path SwiGLU + depthwise conv (kernel 2) of GameConvSwiGLU (game.py:1264-1276) for
-// autograd (agent.GameConvSwiGLU): one thread per channel, a block per board (grid-stride), the 16
-// tokens in a register loop, so the conv's one-token shift is a register carry.  The arithmetic
-// follows the reference's autocast dtypes: y = bf16(bf16(silu(gate)) * up), y2 = y_{t-1} w0 +
+// autograd (agent.GameConvSwiGLU): a thread per channel (forward) or channel pair (forward and
+// backward), boards grid-strided, the 16 tokens in a register loop, so the conv's one-token shift is a
+// register carry.  The arithmetic follows the reference's autocast dtypes: y = bf16(bf16(silu(gate)) * up), y2 = y_{t-1} w0 +
 // y_t w1 + b in fp32, act = silu(y2) (stored bf16: the down_proj operand).  The backward recomputes
 // y and y2 and writes dgate / dup (bf16) and per-block partials of dw0, dw1, db (fp32 [3][inter]).
 constexpr int kScThreads = 128;
@@ -1693,74 +1693,50 @@ __global__ __launch_bounds__(256) void urm_swiglu_conv_fwd2_kernel(const uint16_
     }
 }
 
-__global__ __launch_bounds__(kScThreads) void urm_swiglu_conv_bwd_kernel(const uint16_t *__restrict__ gu,
-                                                                         const float *__restrict__ w,
-                                                                         const float *__restrict__ bias,
-                                                                         const uint16_t *__restrict__ dact,
-                                                                         uint16_t *__restrict__ dgu,
-                                                                         float *__restrict__ part, int64_t nb,
-                                                                         int inter) {
-    const int c = threadIdx.x;
-    if (c >= inter) return;
-    const float w0 = w[2 * c], w1 = w[2 * c + 1], b = bias[c];
-    float s0 = 0.0f, s1 = 0.0f, sb = 0.0f;
-    for (int64_t bd = blockIdx.x; bd < nb; bd += gridDim.x) {
-        float g[16], u[16], y[16], d2[16], sgg[16];
-        float yp = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 16; t++) {
-            const int64_t r = 16 * bd + t;
-            g[t] = bf16f(gu[r * 2 * inter + c]);
-            u[t] = bf16f(gu[r * 2 * inter + inter + c]);
-            sgg[t] = sigm(g[t]);
-            y[t] = bfr(bfr(g[t] * sgg[t]) * u[t]);
-            const float y2 = yp * w0 + y[t] * w1 + b, sg = sigm(y2);
-            d2[t] = bf16f(dact[r * inter + c]) * (sg * (1.0f + y2 * (1.0f - sg)));  // d act / d y2
-            s1 += d2[t] * y[t];
-            s0 += d2[t] * yp;
-            sb += d2[t];
-            yp = y[t];
-        }
-#pragma unroll
-        for (int t = 0; t < 16; t++) {
-            const int64_t r = 16 * bd + t;
-            const float dy = d2[t] * w1 + (t + 1 < 16 ? d2[t + 1] * w0 : 0.0f);
-            const float sg = sgg[t], sl = bfr(g[t] * sg);
-            dgu[r * 2 * inter + c] = f2bf16(dy * u[t] * (sg * (1.0f + g[t] * (1.0f - sg))));
-            dgu[r * 2 * inter + inter + c] = f2bf16(dy * sl);
-        }
-    }
-    float *pp = part + (int64_t)blockIdx.x * 3 * inter;
-    pp[c] = s0;
-    pp[inter + c] = s1;
-    pp[2 * inter + c] = sb;
-}
-
-// The same backward with one thread per channel PAIR (4-byte gu / dact loads and dgu stores) and
-// four partial rows per 256-thread block (64 threads each, inter / 2 <= 64 of them active), the 16
-// tokens in ONE pass with a one-token lag (token t - 1's dgate / dup need d2 of token t): nothing
-// but the board's raw loads is kept in registers.  Partial row `row` takes boards row, row + nrows,
-// ... exactly like block `row` of urm_swiglu_conv_bwd_kernel, with the same per-channel arithmetic,
-// so dgu and the partials are bitwise those of the one-channel kernel.
+// The backward with one thread per channel PAIR and four partial rows per 256-thread block (64 threads
+// each, (inter + 1) / 2 <= 64 of them active), the 16 tokens in ONE pass with a one-token lag (token
+// t - 1's dgate / dup need d2 of token t): nothing but the board's raw loads is kept in registers.
+// Partial row `row` takes boards row, row + nrows, ...  The pair's memory accesses are 4-byte gu /
+// dact loads and dgu stores, or (kNarrow: odd inter, or buffers that are only 2-byte aligned) two 2-byte
+// ones with the missing second channel of an odd inter masked.  Contract: dgu and the partials of the
+// two variants are bitwise equal.  The arithmetic is one body, compiled with contraction off and every FMA
+// written out, so the compiler has no per-variant choice of which products to fuse
+// (tests/test_gpu_urm_block_edges.py holds the contract).
+template <bool kNarrow>
 __global__ __launch_bounds__(256) void urm_swiglu_conv_bwd2_kernel(const uint16_t *__restrict__ gu,
                                                                    const float *__restrict__ w,
                                                                    const float *__restrict__ bias,
                                                                    const uint16_t *__restrict__ dact,
                                                                    uint16_t *__restrict__ dgu, float *__restrict__ part,
                                                                    int64_t nb, int inter, int nrows) {
+#pragma clang fp contract(off)  // every FMA below is written out, so both variants round alike
     const int cp = threadIdx.x & 63, row = (int)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= nrows || 2 * cp >= inter) return;  // no barriers below
     const int c = 2 * cp;
-    const float w0[2] = {w[2 * c], w[2 * c + 2]}, w1[2] = {w[2 * c + 1], w[2 * c + 3]}, bb[2] = {bias[c], bias[c + 1]};
+    const bool two = !kNarrow || c + 1 < inter;  // the pair's second channel exists (always, unless narrow)
+    const float w0[2] = {w[2 * c], two ? w[2 * c + 2] : 0.0f}, w1[2] = {w[2 * c + 1], two ? w[2 * c + 3] : 0.0f},
+                bb[2] = {bias[c], two ? bias[c + 1] : 0.0f};
+    auto ld2 = [=](const uint16_t *p) {  // the pair at p: one 4-byte load, or two 2-byte loads
+        if (!kNarrow) return *reinterpret_cast<const uint32_t *>(p);
+        return (uint32_t)p[0] | (two ? (uint32_t)p[1] << 16 : 0u);
+    };
+    auto st2 = [=](uint16_t *p, uint16_t lo, uint16_t hi) {
+        if (!kNarrow) {
+            *reinterpret_cast<uint32_t *>(p) = (uint32_t)lo | ((uint32_t)hi << 16);
+        } else {
+            p[0] = lo;
+            if (two) p[1] = hi;
+        }
+    };
     float s0[2] = {0.0f, 0.0f}, s1[2] = {0.0f, 0.0f}, sb[2] = {0.0f, 0.0f};
     for (int64_t bd = row; bd < nb; bd += nrows) {
         uint32_t gr[16], ur[16], dr[16];  // the board's 48 loads in flight before any arithmetic
 #pragma unroll
         for (int t = 0; t < 16; t++) {
             const uint16_t *rw = gu + (16 * bd + t) * 2 * inter;
-            gr[t] = *reinterpret_cast<const uint32_t *>(rw + c);
-            ur[t] = *reinterpret_cast<const uint32_t *>(rw + inter + c);
-            dr[t] = *reinterpret_cast<const uint32_t *>(dact + (16 * bd + t) * inter + c);
+            gr[t] = ld2(rw + c);
+            ur[t] = ld2(rw + inter + c);
+            dr[t] = ld2(dact + (16 * bd + t) * inter + c);
         }
         float yp[2] = {0.0f, 0.0f}, gq[2] = {0.0f, 0.0f}, uq[2] = {0.0f, 0.0f}, sq[2] = {0.0f, 0.0f}, dq[2] = {0.0f, 0.0f};
 #pragma unroll
@@ -1775,16 +1751,16 @@ __global__ __launch_bounds__(256) void urm_swiglu_conv_bwd2_kernel(const uint16_
                     const float da = __uint_as_float(j ? dr[t] & 0xFFFF0000u : dr[t] << 16);
                     sg[j] = sigm(g[j]);
                     const float y = bfr(bfr(g[j] * sg[j]) * u[j]);
-                    const float y2 = yp[j] * w0[j] + y * w1[j] + bb[j], s2 = sigm(y2);
-                    d2[j] = da * (s2 * (1.0f + y2 * (1.0f - s2)));  // d act / d y2
-                    s1[j] += d2[j] * y;
-                    s0[j] += d2[j] * yp[j];
+                    const float y2 = fmaf(y, w1[j], fmaf(yp[j], w0[j], bb[j])), s2 = sigm(y2);
+                    d2[j] = da * (s2 * fmaf(y2, 1.0f - s2, 1.0f));  // d act / d y2
+                    s1[j] = fmaf(d2[j], y, s1[j]);
+                    s0[j] = fmaf(d2[j], yp[j], s0[j]);
                     sb[j] += d2[j];
                     yp[j] = y;
                 }
                 if (t > 0) {  // token t - 1
-                    const float dy = dq[j] * w1[j] + (t < 16 ? d2[j] * w0[j] : 0.0f);
-                    og[j] = f2bf16(dy * uq[j] * (sq[j] * (1.0f + gq[j] * (1.0f - sq[j]))));
+                    const float dy = fmaf(dq[j], w1[j], t < 16 ? d2[j] * w0[j] : 0.0f);
+                    og[j] = f2bf16(dy * uq[j] * (sq[j] * fmaf(gq[j], 1.0f - sq[j], 1.0f)));
                     ou[j] = f2bf16(dy * bfr(gq[j] * sq[j]));
                 }
                 gq[j] = g[j];
@@ -1794,14 +1770,15 @@ __global__ __launch_bounds__(256) void urm_swiglu_conv_bwd2_kernel(const uint16_
             }
             if (t > 0) {
                 uint16_t *dw = dgu + (16 * bd + t - 1) * 2 * inter;
-                *reinterpret_cast<uint32_t *>(dw + c) = (uint32_t)og[0] | ((uint32_t)og[1] << 16);
-                *reinterpret_cast<uint32_t *>(dw + inter + c) = (uint32_t)ou[0] | ((uint32_t)ou[1] << 16);
+                st2(dw + c, og[0], og[1]);
+                st2(dw + inter + c, ou[0], ou[1]);
             }
         }
     }
     float *pp = part + (int64_t)row * 3 * inter;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
+        if (j && !two) break;
         pp[c + j] = s0[j];
         pp[inter + c + j] = s1[j];
         pp[2 * inter + c + j] = sb[j];
@@ -2778,11 +2755,11 @@ int g2048_urm_swiglu_conv_bwd(g2048_stream_t stream, const uint16_t *gu, const f
     const hipStream_t s = (hipStream_t)stream;
     const int nblk = sc_blocks(n);
     if (inter % 2 == 0 && inter <= 128 && ((uintptr_t)gu | (uintptr_t)dact | (uintptr_t)dgu) % 4 == 0)
-        hipLaunchKernelGGL(urm_swiglu_conv_bwd2_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, gu, w, b, dact,
-                           dgu, partials, n, (int)inter, nblk);
+        hipLaunchKernelGGL(urm_swiglu_conv_bwd2_kernel<false>, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, gu, w, b,
+                           dact, dgu, partials, n, (int)inter, nblk);
     else
-        hipLaunchKernelGGL(urm_swiglu_conv_bwd_kernel, dim3(nblk), dim3(kScThreads), 0, s, gu, w, b, dact, dgu, partials,
-                           n, (int)inter);
+        hipLaunchKernelGGL(urm_swiglu_conv_bwd2_kernel<true>, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, gu, w, b,
+                           dact, dgu, partials, n, (int)inter, nblk);
     hipLaunchKernelGGL(urm_swiglu_conv_colsum_kernel, dim3((3 * inter + 15) / 16), dim3(256), 0, s, partials, nblk,
                        (int)inter, dw, db, 0);
     return launch_status();
