@@ -157,6 +157,12 @@ __device__ __forceinline__ uint32_t pick_row(uint32_t x, uint32_t y, uint32_t z,
     return (uint32_t)(((i & 2u) ? hi : lo) >> (32u * (i & 1u)));
 }
 
+// x_i by an index i = 0..3 whose two bits come as lane masks (all ones / zero): three v_bitop3
+__device__ __forceinline__ uint32_t pick4m(uint32_t m0, uint32_t m1, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
+    constexpr uint32_t kSel = (kA & kB) | (~kA & kC);  // a ? b : c
+    return bop3<kSel>(m1, bop3<kSel>(m0, x3, x2), bop3<kSel>(m0, x1, x0));
+}
+
 // Statistics after placing exponent v on the EMPTY cell p of board b (the spawn): only the (up to
 // four) pairs through p change, and the max / first-argmax.
 __device__ __forceinline__ MonoStats mono_add_tile(MonoStats s, const uint4 &b, uint32_t p, uint32_t v) {
@@ -263,8 +269,8 @@ __device__ __forceinline__ uint32_t kth_bit16(uint32_t m, uint32_t k) {
 }
 
 // k-th (0-based) set bit of a 4-bit mask m (k < popcount(m)): 2-bit answers packed per k in a
-// 32-bit constant indexed by m
-__device__ __forceinline__ uint32_t kth_bit4(uint32_t m, uint32_t k) {
+// 32-bit constant indexed by m (the compile-time check of kth_bit4 below)
+constexpr uint32_t kth_bit4_table(uint32_t m, uint32_t k) {
     constexpr uint32_t T[4] = {
         [] { uint32_t t = 0; for (uint32_t m = 1; m < 16; m++) { uint32_t j = 0; while (!((m >> j) & 1u)) j++; t |= j << (2 * m); } return t; }(),
         [] { uint32_t t = 0; for (uint32_t m = 1; m < 16; m++) { uint32_t c = 0, j = 0; for (; j < 4; j++) if ((m >> j) & 1u) { if (c == 1) break; c++; } t |= (j & 3u) << (2 * m); } return t; }(),
@@ -273,6 +279,31 @@ __device__ __forceinline__ uint32_t kth_bit4(uint32_t m, uint32_t k) {
     };
     const uint32_t t01 = (k & 1u) ? T[1] : T[0], t23 = (k & 1u) ? T[3] : T[2];
     return ((k & 2u) ? t23 : t01) >> (2u * m) & 3u;
+}
+static_assert(kth_bit4_table(0b1001u, 1u) == 3u && kth_bit4_table(0b1110u, 0u) == 1u, "kth_bit4_table");
+
+// The same for k < popcount(m) without a table or a select, in 6-bit fields: m x 0x8421 puts bit j of
+// m at 6 j (shifts of 0, 5, 10, 15: no two partial products meet), a second multiply sums the fields,
+// so field j (0..2) of c is the number of set bits among bits 0..j of m.  The answer is the number of
+// those three counts that are <= k, and bit 5 of a field of (0x20 + k - c_j) says so: k, c_j <= 3, so
+// no field borrows or carries; what the products leave above bit 17 is masked off.  Seven VALU, three
+// behind k (v_mad_u32_u24, v_and, v_bcnt), for the table form's ten (two compares, three selects).
+constexpr uint32_t kth_bit4_fields(uint32_t m, uint32_t k) {
+    const uint32_t c = ((m * 0x8421u) & 0x41041u) * 0x1041u;
+    uint32_t g = (k * 0x1041u + (0x20820u - c)) & 0x20820u, n = 0u;
+    for (; g; g &= g - 1u) n++;
+    return n;
+}
+constexpr bool kth_bit4_fields_ok() {
+    for (uint32_t m = 1u; m < 16u; m++)
+        for (uint32_t k = 0u, left = m; left; left &= left - 1u, k++)
+            if (kth_bit4_fields(m, k) != kth_bit4_table(m, k)) return false;
+    return true;
+}
+static_assert(kth_bit4_fields_ok(), "the field form against the table for every mask and every k below its popcount");
+__device__ __forceinline__ uint32_t kth_bit4(uint32_t m, uint32_t k) {
+    const uint32_t c = __umul24(__umul24(m, 0x8421u) & 0x41041u, 0x1041u);
+    return __popc((__umul24(k, 0x1041u) + (0x20820u - c)) & 0x20820u);
 }
 
 __device__ __forceinline__ void set_cell(uint4 &b, uint32_t pos, uint32_t v) {

@@ -177,6 +177,9 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     // start-slid half for UP / LEFT, the end-slid one for DOWN / RIGHT (the unpack selector).  No
     // table read and no address arithmetic: the previous step read these records.
     const bool vert = a < 2u, rev = (a & 1u) != 0u;
+    // (a select: kUnpackEndSel is kUnpackStartSel | 0x02020202, but that constant is wider than a
+    // 24-bit multiply-add takes, and the mask form -- v_bfe_i32, v_and, v_or for v_and, v_cmp,
+    // v_cndmask -- split the loop header and ran 7 % slower: DESIGN.md section 6, round 13)
     const uint32_t usel = rev ? kUnpackEndSel : kUnpackStartSel;
     const uint32_t e0 = vert ? s.C[0].x : s.R[0].x, e1 = vert ? s.C[1].x : s.R[1].x;
     const uint32_t e2 = vert ? s.C[2].x : s.R[2].x, e3 = vert ? s.C[3].x : s.R[3].x;
@@ -212,19 +215,53 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const uint64_t prod = (uint64_t)r * empt_a;
     const uint32_t k = (uint32_t)(prod >> 32);
     const uint32_t v = (uint32_t)prod < kTwoThreshold ? 1u : 2u;
-    const bool r1 = k >= n0, r2 = k >= n01, r3 = k >= n012;  // spawn row >= 1, >= 2, == 3
-    const uint32_t kr = k - (r3 ? n012 : r2 ? n01 : r1 ? n0 : 0u);
-    const uint32_t z = r3 ? Zm[3] : r2 ? Zm[2] : r1 ? Zm[1] : Zm[0];
-    const uint32_t b0 = (z >> 7) & 1u, b01 = b0 + ((z >> 15) & 1u), b012 = b01 + ((z >> 23) & 1u);
-    const bool c1 = kr >= b0, c2 = kr >= b01, c3 = kr >= b012;  // spawn column >= 1, >= 2, == 3
-    const uint32_t row = (uint32_t)r1 + (uint32_t)r2 + (uint32_t)r3, col = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
-    const uint32_t sp = 4u * row + col;
+    // The row without a compare or a select: bytes 0..2 of P hold the empties above rows 1, 2, 3
+    // (byte 3 stays 0), and bit 7 of a byte of (0x80 + k - P_i) says k >= P_i: k <= 15 and P_i <= 12, so
+    // no byte borrows or carries.  The row is the count of those bits, the empties above it byte
+    // row - 1 of P (v_bfe_u32 reads its offset from bits 0..4: row 0 reads byte 3, a zero).  The column
+    // inside the row z likewise, from the prefix counts of its cells 0..2 (a multiply sums bits 0, 8,
+    // 16 of z >> 7 into bytes 0..2; v_mul_u32_u24 drops bit 24, cell 3, and what the product leaves in
+    // byte 3 is masked off).  The picks by row and column (z, the address of the spawn's row / column
+    // record, the dword the tile goes into) take the two bits of the index as lane masks.
     const uint4 pre = moved;
-    const uint32_t bits = v << (8u * col);
-    moved.x |= r1 ? 0u : bits;
-    moved.y |= (r1 && !r2) ? bits : 0u;
-    moved.z |= (r2 && !r3) ? bits : 0u;
-    moved.w |= r3 ? bits : 0u;
+    uint32_t row, col, mr0 = 0u, mr1 = 0u, mc0 = 0u, mc1 = 0u;
+    bool r1 = false, r2 = false, r3 = false, c1 = false, c2 = false, c3 = false;
+    if constexpr (kTraj) {
+        const uint32_t P = n0 | (n01 << 8) | (n012 << 16);
+        const uint32_t ger = (__umul24(k, 0x010101u) + (0x808080u - P)) & 0x808080u;
+        row = __popc(ger);
+        const uint32_t kr = k - __builtin_amdgcn_ubfe(P, 8u * row - 8u, 8u);
+        mr0 = (uint32_t)__builtin_amdgcn_sbfe((int)row, 0u, 1u), mr1 = (uint32_t)__builtin_amdgcn_sbfe((int)ger, 15u, 1u);
+        asm("" : "+v"(mr0), "+v"(mr1));
+        const uint32_t z = pick4m(mr0, mr1, Zm[0], Zm[1], Zm[2], Zm[3]);
+        const uint32_t PC = __umul24(z >> 7, 0x010101u);
+        const uint32_t gec = (__umul24(kr, 0x010101u) + (0x808080u - PC)) & 0x808080u;
+        col = __popc(gec);
+        mc0 = (uint32_t)__builtin_amdgcn_sbfe((int)col, 0u, 1u), mc1 = (uint32_t)__builtin_amdgcn_sbfe((int)gec, 15u, 1u);
+        asm("" : "+v"(mc0), "+v"(mc1));
+        const uint32_t bits = v << (8u * col);
+        const uint32_t blo = bop3<~kA & kB>(mr1, bits, 0u), bhi = mr1 & bits;  // the tile for rows 0 / 1, for rows 2 / 3
+        moved.x = bop3<kA | (~kB & kC)>(moved.x, mr0, blo);
+        moved.y = bop3<kA | (kB & kC)>(moved.y, mr0, blo);
+        moved.z = bop3<kA | (~kB & kC)>(moved.z, mr0, bhi);
+        moved.w = bop3<kA | (kB & kC)>(moved.w, mr0, bhi);
+    } else {
+        // the search's step keeps the compare-and-select form: at its 117 VGPRs the masks and the packed
+        // words above cost it 11 more registers and scratch, and it ran 2.3 % slower with them
+        // (profiles/r13a/time_mc_search_ab_masks.log)
+        r1 = k >= n0, r2 = k >= n01, r3 = k >= n012;  // spawn row >= 1, >= 2, == 3
+        const uint32_t kr = k - (r3 ? n012 : r2 ? n01 : r1 ? n0 : 0u);
+        const uint32_t z = r3 ? Zm[3] : r2 ? Zm[2] : r1 ? Zm[1] : Zm[0];
+        const uint32_t b0 = (z >> 7) & 1u, b01 = b0 + ((z >> 15) & 1u), b012 = b01 + ((z >> 23) & 1u);
+        c1 = kr >= b0, c2 = kr >= b01, c3 = kr >= b012;  // spawn column >= 1, >= 2, == 3
+        row = (uint32_t)r1 + (uint32_t)r2 + (uint32_t)r3, col = (uint32_t)c1 + (uint32_t)c2 + (uint32_t)c3;
+        const uint32_t bits = v << (8u * col);
+        moved.x |= r1 ? 0u : bits;
+        moved.y |= (r1 && !r2) ? bits : 0u;
+        moved.z |= (r2 && !r3) ? bits : 0u;
+        moved.w |= r3 ? bits : 0u;
+    }
+    const uint32_t sp = 4u * row + col;
     s.b = moved;  // the next board (after the spawn)
     // The step's one LDS round trip: the records of the next board's four rows and four columns (the
     // next move, whatever its direction, and this board's line sums), and (kTraj) the line entries of
@@ -242,7 +279,8 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     uint32_t ra[4], ca[4];
     line11_addrs(ab, ra, ca);
     constexpr uint64_t kW11 = 0x299803C800580008ull;  // 8 x {1, 11, 121, 1331}
-    const uint32_t rq = r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0], cq = c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];
+    const uint32_t rq = kTraj ? pick4m(mr0, mr1, ra[0], ra[1], ra[2], ra[3]) : r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0];
+    const uint32_t cq = kTraj ? pick4m(mc0, mc1, ca[0], ca[1], ca[2], ca[3]) : c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];
     const uint32_t rp = rq - va * ((uint32_t)(kW11 >> (16u * col)) & 0xFFFFu);
     const uint32_t cp = cq - va * ((uint32_t)(kW11 >> (16u * row)) & 0xFFFFu);
     uint2 R0 = lds_rec(tab, ra[0]), R1 = lds_rec(tab, ra[1]), R2 = lds_rec(tab, ra[2]), R3 = lds_rec(tab, ra[3]);
