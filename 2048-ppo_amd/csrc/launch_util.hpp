@@ -1,7 +1,7 @@
 // launch_util.hpp -- host-side helpers shared by the libg2048 translation units that launch the
-// env and search kernels (g2048.hip, env_rollout.hip, mc_search.hip, expectimax.hip, ntuple.hip): the
-// launch status, the alignment and g2048_rng checks, the RngArgs copy and the launch shape of the
-// kernels that keep the kLine11 tables in LDS.
+// env and search kernels (g2048.hip, env_rollout.hip, mc_search.hip, expectimax.hip, ntuple.hip,
+// ntuple_search.hip): the launch status, the alignment and g2048_rng checks, the RngArgs copy and the
+// launch shape of the kernels that keep the kLine11 tables in LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,110 @@
+// ntuple_net.hpp -- the n-tuple network as the kernels of ntuple.hip and ntuple_search.hip take it
+// (include/g2048_ntuple.h): the kernel argument NtArgs and the host code that packs a g2048_ntuple_net
+// into it, the board packed into 16 nibbles, the table index of a (tuple, symmetry) and V(b).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "board.hpp"
+#include "launch_util.hpp"
+#include "../../include/g2048_ntuple.h"
+
+namespace {
+
+using namespace g2048;
+
+constexpr int kMaxT = G2048_NT_MAX_TUPLES, kMaxK = G2048_NT_MAX_LEN, kFrac = G2048_NT_FRAC_BITS;
+static_assert(kMaxT * kMaxK == 48, "g2048_ntuple_net.cells holds T x K cells");
+
+// The net as the kernels take it: cells[8 t + g] = the K cells of tuple t under symmetry g, 4 bits each
+// (cell j in bits 4 j ..), so that idx_t(g(b)) = sum_j e(b, cell j) << 4 j.
+struct NtArgs {
+    uint32_t cells[8 * kMaxT];
+    int32_t *w;
+    int32_t T;
+};
+
+// min(exponent, 15) of the 16 cells of a board in the nibbles of one word: cell c in bits 4 c .. 4 c + 3
+__device__ __forceinline__ uint32_t nt_pack_row(uint32_t r) {
+    const uint32_t ge = gem(r, 0x10101010u);   // bit 7 of the bytes >= 16
+    const uint32_t m = ge | (ge - (ge >> 7));  // 0xFF in those bytes
+    const uint32_t c = (r & ~m) | (m & 0x0F0F0F0Fu);
+    const uint32_t p = (c | (c >> 4)) & 0x00FF00FFu;
+    return (p | (p >> 8)) & 0xFFFFu;
+}
+__device__ __forceinline__ uint64_t nt_pack(const uint4 &b) {
+    const uint32_t lo = nt_pack_row(b.x) | (nt_pack_row(b.y) << 16), hi = nt_pack_row(b.z) | (nt_pack_row(b.w) << 16);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+template <int K>
+__device__ __forceinline__ uint32_t nt_index(uint64_t x, uint32_t cells) {
+    uint32_t idx = 0u;
+#pragma unroll
+    for (int j = 0; j < K; j++) idx |= ((uint32_t)(x >> (4u * ((cells >> (4 * j)) & 15u))) & 15u) << (4 * j);
+    return idx;
+}
+
+// V(b): the 8 gathers of a tuple are issued together
+template <int K>
+__device__ __forceinline__ int64_t nt_value(const NtArgs &net, uint64_t x) {
+    int64_t v = 0;
+    for (int t = 0; t < net.T; t++) {
+        const int32_t *W = net.w + ((size_t)t << (4 * K));
+        int32_t w[8];
+#pragma unroll
+        for (int g = 0; g < 8; g++) w[g] = W[nt_index<K>(x, net.cells[8 * t + g])];
+#pragma unroll
+        for (int g = 0; g < 8; g++) v += w[g];
+    }
+    return v;
+}
+
+// cell c = 4 r + col under symmetry s of the square: s & 4 transposes, then s & 3 quarter turns
+inline int sym_cell(int c, int s) {
+    int r = c >> 2, col = c & 3;
+    if (s & 4) {
+        const int x = r;
+        r = col;
+        col = x;
+    }
+    for (int k = 0; k < (s & 3); k++) {
+        const int x = r;
+        r = col;
+        col = 3 - x;
+    }
+    return 4 * r + col;
+}
+
+// false: the net is refused
+inline bool make_args(const g2048_ntuple_net *net, NtArgs &out) {
+    if (!net) return false;
+    const int T = net->num_tuples, K = net->tuple_len;
+    if (T < 1 || T > kMaxT || K < 1 || K > kMaxK || !net->weights || !aligned16(net->weights)) return false;
+    out = NtArgs{};
+    out.w = net->weights;
+    out.T = T;
+    for (int t = 0; t < T; t++) {
+        uint32_t seen = 0u;
+        for (int j = 0; j < K; j++) {
+            const int c = net->cells[K * t + j];
+            if (c < 0 || c > 15 || ((seen >> c) & 1u)) return false;
+            seen |= 1u << c;
+            for (int s = 0; s < 8; s++) out.cells[8 * t + s] |= (uint32_t)sym_cell(c, s) << (4 * j);
+        }
+    }
+    return true;
+}
+
+// fn<K>(args...) for the run-time tuple length
+#define G2048_NT_DISPATCH(K, CALL) \
+    switch (K) {                   \
+    case 1: { constexpr int kK = 1; CALL; } break; \
+    case 2: { constexpr int kK = 2; CALL; } break; \
+    case 3: { constexpr int kK = 3; CALL; } break; \
+    case 4: { constexpr int kK = 4; CALL; } break; \
+    case 5: { constexpr int kK = 5; CALL; } break; \
+    default: { constexpr int kK = 6; CALL; } break; \
+    }
+
+}  // namespace

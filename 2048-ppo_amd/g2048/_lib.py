@@ -320,6 +320,31 @@ def ntuple_choose(net: NtNet, boards, q=None, legal=None, best=None):
           _dev(q, torch.int64, "q"), _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), n)
 
 
+def ntuple_search_workspace_bytes(n: int, depth: int, form: int = EMAX_AUTO) -> int:
+    """0 for arguments g2048_ntuple_search would refuse."""
+    return int(load().g2048_ntuple_search_workspace_bytes(int(n), int(depth), int(form)))
+
+
+def ntuple_search(net: NtNet, boards, depth: int, q, leaves=None, legal=None, best=None, workspace=None,
+                  form: int = EMAX_AUTO):
+    """Expectimax search with the net at the leaves (g2048_ntuple_search): boards int8 [n, 16] -> q int64
+    [n, 4] (INT64_MIN: illegal), leaves int64 [n, 4], legal / best uint8 [n] (the last three optional).
+    workspace: a uint8 device tensor of ntuple_search_workspace_bytes(n, depth, form) bytes (zero-filled
+    by the call)."""
+    n = boards.shape[0]
+    if q is None:
+        raise G2048Error("ntuple_search: q is required")
+    for t, nm, k in ((q, "q", 4 * n), (leaves, "leaves", 4 * n), (legal, "legal", n), (best, "best", n)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_search: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("ntuple_search: a workspace of ntuple_search_workspace_bytes(n, depth, form) bytes "
+                         "is required")
+    _call("g2048_ntuple_search", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"), n, int(depth),
+          int(form), _dev(q, torch.int64, "q"), _dev(leaves, torch.int64, "leaves"), _dev(legal, torch.uint8, "legal"),
+          _dev(best, torch.uint8, "best"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
+
+
 def ntuple_td_workspace_bytes(n: int) -> int:
     """0 for an n g2048_ntuple_td would refuse."""
     return int(load().g2048_ntuple_td_workspace_bytes(int(n)))

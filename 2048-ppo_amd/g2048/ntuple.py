@@ -6,7 +6,8 @@ board is the sum of the 8 T weights its tuples index under the 8 symmetries of t
 4096.  NTupleTrainer: `envs` games learning in parallel on one net (g2048_ntuple_td): every env plays the
 move of the largest points + value and moves the weights of its previous after-state towards that
 maximum; the updates are integer adds, so a run is reproducible bit for bit.  NTuplePlayer: the greedy
-player of a net (g2048_ntuple_choose) in search.py's game loop.
+player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
+search.py's game loop.
 """
 
 from __future__ import annotations
@@ -14,7 +15,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib as L
-from .search import _SearchPlayer
+from .search import EMAX_FORMS, _SearchPlayer
 
 PRESETS = {
     "lines-squares-4": [[0, 1, 2, 3], [4, 5, 6, 7], [0, 1, 4, 5], [1, 2, 5, 6], [5, 6, 9, 10]],
@@ -22,6 +23,7 @@ PRESETS = {
 }
 MAX_TUPLES, MAX_LEN, FRAC_BITS = L.NT_MAX_TUPLES, L.NT_MAX_LEN, L.NT_FRAC_BITS
 MAX_ENVS = (1 << 28) - 1
+MAX_SEARCH_DEPTH = 3
 
 
 def _check_cells(cells) -> list[list[int]]:
@@ -125,26 +127,46 @@ class NTupleTrainer:
 
 
 class NTuplePlayer(_SearchPlayer):
-    """Plays the move of the largest points + V(after-state) of `net`; it draws nothing."""
+    """Plays the move of the largest points + V(after-state) of `net` (depth 1, g2048_ntuple_choose) or of
+    the largest expectimax value over `depth` in 2..3 moves, the root move included, with V at the leaves
+    (g2048_ntuple_search; form "auto" / "narrow" / "wide": the lane mapping, the results do not depend on
+    it).  It draws nothing."""
 
-    def __init__(self, net: NTupleNet):
+    def __init__(self, net: NTupleNet, depth: int = 1, form: str = "auto"):
         if not isinstance(net, NTupleNet):
             raise ValueError(f"NTuplePlayer needs an NTupleNet, got {type(net).__name__}")
-        self.net = net
+        depth = int(depth)
+        if not 1 <= depth <= MAX_SEARCH_DEPTH:
+            raise ValueError(f"depth must be in [1, {MAX_SEARCH_DEPTH}], got {depth}")
+        if form not in EMAX_FORMS:
+            raise ValueError(f"form must be one of {sorted(EMAX_FORMS)}, got {form!r}")
+        if form == "wide" and depth < 2:
+            raise ValueError("form 'wide' needs depth >= 2")
+        self.net, self.depth, self.form = net, depth, form
         self.device = net.device
 
     def _buffers(self, n: int):
         d = self.device
-        return (torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, 4, dtype=torch.int64, device=d),
+        bufs = (torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, 4, dtype=torch.int64, device=d),
                 torch.empty(n, dtype=torch.uint8, device=d))
+        if self.depth == 1:
+            return bufs
+        nbytes = L.ntuple_search_workspace_bytes(n, self.depth, EMAX_FORMS[self.form])
+        if nbytes == 0:
+            raise ValueError(f"{n} boards are too many for form {self.form!r}")
+        return bufs + (torch.empty(nbytes, dtype=torch.uint8, device=d),)
 
     def _search(self, boards, move_index: int, bufs):
-        best, q, legal = bufs
-        L.ntuple_choose(self.net.c, boards, q, legal, best)
+        if self.depth == 1:
+            best, q, legal = bufs
+            L.ntuple_choose(self.net.c, boards, q, legal, best)
+        else:
+            best, q, legal, ws = bufs
+            L.ntuple_search(self.net.c, boards, self.depth, q, None, legal, best, ws, EMAX_FORMS[self.form])
 
     def choose(self, boards: torch.Tensor):
         """boards int8 [n, 16] -> (best uint8 [n] (0xFF: no legal move), q int64 [n, 4] (INT64_MIN:
         illegal), legal uint8 [n])."""
         bufs = self._buffers(boards.shape[0])
         self._search(boards, 0, bufs)
-        return bufs
+        return bufs[:3]

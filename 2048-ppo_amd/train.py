@@ -426,11 +426,16 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
 def play_ntuple(model_path: Path = typer.Argument(..., metavar="MODEL", help="a net saved by train-ntuple"),
                 games: int = typer.Option(100, "--games", "-g"),
                 max_moves: Optional[int] = typer.Option(None, "--max-moves",
-                                                        help="stop every game after this many moves")):
+                                                        help="stop every game after this many moves"),
+                depth: int = typer.Option(1, "--depth", help="moves looked ahead, the root move included (1..3)")):
     """Play `games` seeded games (game i spawns like random.seed(i), as `evaluate`) with the greedy
-    player of a trained n-tuple network."""
-    from g2048.ntuple import NTupleNet, NTuplePlayer
-    player = NTuplePlayer(NTupleNet.load(model_path, torch.device("cuda", 0)))
+    player of a trained n-tuple network, or with --depth 2 or 3 its expectimax player: the same values
+    at the leaves of a search over every move and spawn."""
+    from g2048.ntuple import MAX_SEARCH_DEPTH, NTupleNet, NTuplePlayer
+    if not 1 <= depth <= MAX_SEARCH_DEPTH:
+        typer.echo(f"Error: --depth must be in 1..{MAX_SEARCH_DEPTH}, got {depth}")
+        raise typer.Exit(1)
+    player = NTuplePlayer(NTupleNet.load(model_path, torch.device("cuda", 0)), depth)
     _echo_results(player.play_games(games, max_moves, seeds=list(range(games))))
 
 

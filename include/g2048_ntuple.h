@@ -40,6 +40,28 @@
  * Range.  The weights WRAP on overflow (two's complement): one weight holds +-2^31 / S = +-2^19
  * points.  Concurrent envs add up on shared weights, so a usable lr_shift grows with n: from zero
  * weights, five 4-tuples and n = 256, lr_shift 9 drove weights to 2^31 while lr_shift 10 learned.
+ *
+ * The search (g2048_ntuple_search).  Expectimax with V at the leaves: d = depth in 1..3 moves looked
+ * ahead, the root move included; E(s) = the number of empty cells of s; s + t@c = s with exponent t
+ * put on its empty cell c.  All values are int64 in points x S.
+ *   A(s, 0) = V(s)                                                  leaf: an after-state
+ *   A(s, k) = floor( sum over the empty cells c of s of (9 M(s + 1@c, k) + M(s + 2@c, k)) / (10 E(s)) ),  k >= 1
+ *   M(b, k) = max over the legal a of (S pts(b, a) + A(move(b, a), k - 1));   0 without a legal move
+ *   q[i][a] = S pts(root_i, a) + A(move(root_i, a), d - 1) for a legal a,  INT64_MIN for an illegal a
+ *   best    = the legal action of the largest q, the lowest index among equals, 0xFF without a legal move
+ *   legal   = bits 0-3, the conventions of g2048_ntuple_choose
+ *   leaves[i][a] = the number of A(., 0) evaluations under root action a, 0 for an illegal one
+ * At d = 1 this is g2048_ntuple_choose bit for bit.  Three points differ from g2048_expectimax:
+ * Values are signed.  Weights are any int32, so V, M and the chance sums can be negative.  floor is the
+ * floor towards minus infinity (Python's //), not C's truncating /.  Illegal actions are marked
+ * INT64_MIN, as in g2048_ntuple_choose, because -1 is a valid value here.  The maximum over the legal
+ * moves starts from "none": only a board without a legal move yields 0, the terminal target of the TD
+ * step -- so a dead position can be better than a live one of negative value; that is intended.
+ * The sum inside A is exact before its one division: no result depends on summation order or on the
+ * lane mapping (`form`).
+ * Bound.  |V| <= 64 x 2^31 = 2^37; S pts < 2^31 per ply, so |M| < 2^38 for d <= 3; a chance node sums at
+ * most 160 weighted terms, |sum| < 2^46.  The signed floor is the unsigned one of sum + 10 E 2^40
+ * (< 2^48), minus 2^40: exact.  Depth 4 is out of scope.
  */
 #ifndef G2048_NTUPLE_H
 #define G2048_NTUPLE_H
@@ -91,6 +113,21 @@ size_t g2048_ntuple_td_workspace_bytes(int64_t n);
 int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
                     uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                     const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
+
+/* Expectimax search of depth 1..3 with V at the leaves (the search, above) on n boards: q int64 [n][4]
+   (16-B aligned, required), leaves int64 [n][4] (nullable, 16-B aligned), legal / best uint8 [n]
+   (nullable).  boards [n,16] is only read.  form: G2048_EMAX_AUTO / _NARROW (one workgroup per board) /
+   _WIDE (one per (board, action, first spawn), depth >= 2) of g2048.h; the results do not depend on
+   it, and AUTO picks a form the call accepts.  workspace: g2048_ntuple_search_workspace_bytes(n, depth,
+   form) bytes, 16-B aligned, zero-filled by the call itself (0 is returned for arguments the call
+   would refuse).  G2048_EINVAL, with nothing enqueued, for a net g2048_ntuple_weight_count refuses,
+   depth outside 1..3, an unknown form, WIDE with depth < 2, n < 0 or a lane count (128 n NARROW,
+   16384 n WIDE) >= 2^31, a null or misaligned boards / q / workspace, a misaligned leaves, a too small
+   workspace. */
+size_t g2048_ntuple_search_workspace_bytes(int64_t n, int64_t depth, int32_t form);
+int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t n,
+                        int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal, uint8_t *best,
+                        void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
