@@ -68,13 +68,89 @@ __device__ __forceinline__ uint32_t lds_half(const uint32_t *tab, uint32_t addr)
 }
 
 // nibble-packed line (dword 0 of a kLine11 record) -> line dword with one exponent per byte, the
-// start-slid half (bits 0..15) or the end-slid half (bits 16..31) by the lane's selector: nibble j of
-// a half is the low nibble of byte j/2 of e (j even) or of e >> 4 (j odd), so one v_perm over
-// (e >> 4, e) places all four and a mask clears the high nibbles.
-constexpr uint32_t kUnpackStartSel = 0x05010400u;  // bytes {n0, n1, n2, n3}
-constexpr uint32_t kUnpackEndSel = 0x07030602u;    // bytes {n4, n5, n6, n7}
-__device__ __forceinline__ uint32_t unpack_row(uint32_t e, uint32_t sel) {
-    return __builtin_amdgcn_perm(e >> 4, e, sel) & 0x0F0F0F0Fu;
+// start-slid half (bits 0..15) or the end-slid half (bits 16..31) by the selector: nibble j of a half
+// is the low nibble of byte j/2 of e (j even) or of e >> 4 (j odd), so one v_perm over (e >> 4, e)
+// places all four and a mask clears the high nibbles ("unpack_row": the step did this per line up to
+// round 13; unpack_transpose_model below keeps it as the reference of the network that replaced it).
+constexpr uint32_t kUnpackStartSel = 0x05010400u;  // bytes {n0, n1, n2, n3}: an interleave of the low byte pairs
+constexpr uint32_t kUnpackEndSel = 0x07030602u;    // bytes {n4, n5, n6, n7}: of the high byte pairs
+
+// The moved board from dword 0 of the four slid lines' records e0..e3 (rows for a horizontal move,
+// columns for a vertical one) without an unpack per line, a transpose and a select per row.  One
+// v_perm packs the chosen halves of two lines into a register (lines 0 and 2, lines 1 and 3), in the
+// byte order {A.b0, A.b1, B.b0, B.b1} for a horizontal move and {A.b0, B.b0, A.b1, B.b1} for a vertical
+// one; the end-slid half is the start-slid selector + 2 in every byte.  Split into low and high
+// nibbles, the 16 digits d(line, position) then sit one per byte:
+//                 horizontal                 vertical
+//   xl02   d00 d02 d20 d22            d00 d20 d02 d22
+//   xh02   d01 d03 d21 d23            d01 d21 d03 d23
+//   xl13   d10 d12 d30 d32            d10 d30 d12 d32
+//   xh13   d11 d13 d31 d33            d11 d31 d13 d33
+// and every row of the board is the same byte interleave in both orientations (kUnpackStartSel for
+// rows 0 / 1, kUnpackEndSel for rows 2 / 3); only one source of each pair depends on the orientation:
+// rows 0 / 2 interleave xl02 with xh02 (horizontal: d00 d01 d02 d03) or xl13 (vertical: d00 d10 d20
+// d30), rows 1 / 3 interleave xl13 (horizontal) or xh02 (vertical) with xh13.  2 perms, 2 shifts, 4
+// ands, 2 selects and 4 perms behind the selector, for 12 + 8 + 4 of unpack_row x 4, transpose, sel4.
+constexpr uint32_t kPackRowsSel = 0x05040100u;  // horizontal, start-slid: bytes {A.b0, A.b1, B.b0, B.b1}
+constexpr uint32_t kPackColsSel = 0x05010400u;  // vertical, start-slid: bytes {A.b0, B.b0, A.b1, B.b1}
+constexpr uint32_t kPackEndAdd = 0x02020202u;   // + this: the end-slid halves
+// v_perm_b32 for the selector bytes the step uses (0..3 bytes of lo, 4..7 bytes of hi, 0x0C zero)
+constexpr uint32_t perm_model(uint32_t hi, uint32_t lo, uint32_t sel) {
+    const uint64_t src = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0u;
+    for (uint32_t j = 0u; j < 4u; j++) {
+        const uint32_t s = (sel >> (8u * j)) & 0xFFu;
+        r |= (s < 8u ? (uint32_t)(src >> (8u * s)) & 0xFFu : 0u) << (8u * j);
+    }
+    return r;
+}
+struct Rows4 {  // uint4 has no constexpr constructor
+    uint32_t x, y, z, w;
+};
+constexpr Rows4 orient_rows_model(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, bool vert, bool rev) {
+    const uint32_t psel = (vert ? kPackColsSel : kPackRowsSel) + (rev ? kPackEndAdd : 0u);
+    const uint32_t x02 = perm_model(e2, e0, psel), x13 = perm_model(e3, e1, psel);
+    const uint32_t xl02 = x02 & 0x0F0F0F0Fu, xh02 = (x02 >> 4) & 0x0F0F0F0Fu;
+    const uint32_t xl13 = x13 & 0x0F0F0F0Fu, xh13 = (x13 >> 4) & 0x0F0F0F0Fu;
+    const uint32_t pA = vert ? xl13 : xh02, pB = vert ? xh02 : xl13;
+    return Rows4{perm_model(pA, xl02, kUnpackStartSel), perm_model(xh13, pB, kUnpackStartSel),
+                 perm_model(pA, xl02, kUnpackEndSel), perm_model(xh13, pB, kUnpackEndSel)};
+}
+// unpack_row x 4, board.hpp's transpose and sel4(vert, ...), the form the network replaces
+constexpr Rows4 unpack_transpose_model(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, bool vert, bool rev) {
+    const uint32_t usel = rev ? kUnpackEndSel : kUnpackStartSel;
+    const uint32_t w[4] = {perm_model(e0 >> 4, e0, usel) & 0x0F0F0F0Fu, perm_model(e1 >> 4, e1, usel) & 0x0F0F0F0Fu,
+                           perm_model(e2 >> 4, e2, usel) & 0x0F0F0F0Fu, perm_model(e3 >> 4, e3, usel) & 0x0F0F0F0Fu};
+    const uint32_t p = perm_model(w[1], w[0], 0x05010400u), q = perm_model(w[1], w[0], 0x07030602u);
+    const uint32_t u = perm_model(w[3], w[2], 0x05010400u), v = perm_model(w[3], w[2], 0x07030602u);
+    if (!vert) return Rows4{w[0], w[1], w[2], w[3]};
+    return Rows4{perm_model(u, p, 0x05040100u), perm_model(u, p, 0x07060302u), perm_model(v, q, 0x05040100u),
+                 perm_model(v, q, 0x07060302u)};
+}
+// both orientations, both halves, and record words that put every digit 0..10 in every nibble
+// position of every one of the four records (digit (k + 3 j + 5 i) mod 11 in nibble j of record i)
+constexpr bool orient_rows_ok() {
+    for (uint32_t k = 0u; k < 11u; k++) {
+        uint32_t e[4] = {0u, 0u, 0u, 0u};
+        for (uint32_t i = 0u; i < 4u; i++)
+            for (uint32_t j = 0u; j < 8u; j++) e[i] |= ((k + 3u * j + 5u * i) % 11u) << (4u * j);
+        for (uint32_t o = 0u; o < 4u; o++) {
+            const Rows4 n = orient_rows_model(e[0], e[1], e[2], e[3], (o & 2u) != 0u, (o & 1u) != 0u);
+            const Rows4 r = unpack_transpose_model(e[0], e[1], e[2], e[3], (o & 2u) != 0u, (o & 1u) != 0u);
+            if (n.x != r.x || n.y != r.y || n.z != r.z || n.w != r.w) return false;
+        }
+    }
+    return true;
+}
+static_assert(orient_rows_ok(), "the orientation network against unpack_row, transpose and sel4");
+// psel = the pack selector of the move (orient_rows_model's)
+__device__ __forceinline__ uint4 orient_rows(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, uint32_t psel, bool vert) {
+    const uint32_t x02 = __builtin_amdgcn_perm(e2, e0, psel), x13 = __builtin_amdgcn_perm(e3, e1, psel);
+    const uint32_t xl02 = x02 & 0x0F0F0F0Fu, xh02 = (x02 >> 4) & 0x0F0F0F0Fu;
+    const uint32_t xl13 = x13 & 0x0F0F0F0Fu, xh13 = (x13 >> 4) & 0x0F0F0F0Fu;
+    const uint32_t pA = vert ? xl13 : xh02, pB = vert ? xh02 : xl13;
+    return make_uint4(__builtin_amdgcn_perm(pA, xl02, kUnpackStartSel), __builtin_amdgcn_perm(xh13, pB, kUnpackStartSel),
+                      __builtin_amdgcn_perm(pA, xl02, kUnpackEndSel), __builtin_amdgcn_perm(xh13, pB, kUnpackEndSel));
 }
 
 // Copy the tables (kLine11, kFresh, kFreshLines) into LDS by LDS-DMA: each wave instruction moves 1 KiB (16 B per lane)

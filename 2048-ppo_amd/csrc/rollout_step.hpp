@@ -174,20 +174,22 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const uint64_t pa = (uint64_t)u * (uint32_t)__popc(s.legal);
     const uint32_t a = kth_bit4(s.legal, (uint32_t)(pa >> 32)), r = (uint32_t)pa;
     // the move from the carried records: the columns' for UP / DOWN, the rows' otherwise; the
-    // start-slid half for UP / LEFT, the end-slid one for DOWN / RIGHT (the unpack selector).  No
-    // table read and no address arithmetic: the previous step read these records.
+    // start-slid half for UP / LEFT, the end-slid one for DOWN / RIGHT (the pack selector of
+    // line11_lds.hpp's orient_rows).  No table read and no address arithmetic: the previous step read
+    // these records.
     const bool vert = a < 2u, rev = (a & 1u) != 0u;
-    // (a select: kUnpackEndSel is kUnpackStartSel | 0x02020202, but that constant is wider than a
-    // 24-bit multiply-add takes, and the mask form -- v_bfe_i32, v_and, v_or for v_and, v_cmp,
-    // v_cndmask -- split the loop header and ran 7 % slower: DESIGN.md section 6, round 13)
-    const uint32_t usel = rev ? kUnpackEndSel : kUnpackStartSel;
     const uint32_t e0 = vert ? s.C[0].x : s.R[0].x, e1 = vert ? s.C[1].x : s.R[1].x;
     const uint32_t e2 = vert ? s.C[2].x : s.R[2].x, e3 = vert ? s.C[3].x : s.R[3].x;
     const uint32_t h0 = vert ? s.C[0].y : s.R[0].y, h1 = vert ? s.C[1].y : s.R[1].y;
     const uint32_t h2 = vert ? s.C[2].y : s.R[2].y, h3 = vert ? s.C[3].y : s.R[3].y;
     const uint32_t mono_b = kTraj ? mono_value_packed(s.S) : 0u;
-    const uint4 w = make_uint4(unpack_row(e0, usel), unpack_row(e1, usel), unpack_row(e2, usel), unpack_row(e3, usel));
-    uint4 moved = sel4(vert, transpose(w), w);
+    // (two selects and an add: kPackEndAdd is wider than a 24-bit multiply-add takes.  The mask form --
+    // v_bfe_i32 and v_and_or behind the select by vert, two VALU fewer per step -- measured 1.5 % slower
+    // than this one, as the unpack selector's did in round 13, and a select among the four constants
+    // costs scratch: DESIGN.md section 6, round 14)
+    const uint32_t pbase = vert ? kPackColsSel : kPackRowsSel;
+    const uint32_t psel = rev ? pbase + kPackEndAdd : pbase;
+    uint4 moved = orient_rows(e0, e1, e2, e3, psel, vert);
     // merge points / 4 in bits 16..27 of each record's dword 1, the slid line's maximum in bits 28..31
     uint32_t pts = (((h0 >> 16) & 0xFFFu) + ((h1 >> 16) & 0xFFFu) + ((h2 >> 16) & 0xFFFu) + ((h3 >> 16) & 0xFFFu)) << 2;
     uint32_t Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(h0), as_u16x2(h1)),
