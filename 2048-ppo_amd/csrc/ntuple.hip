@@ -11,6 +11,10 @@
 // no-return 32-bit atomic adds of the same shape.  A TD step is two launches: nt_td_eval_kernel only
 // reads the weights (choice, target, delta), nt_td_update_kernel only adds to them and steps the env,
 // and stream order between the two makes every read see the weights before the step's updates.
+// A TC step (temporal-coherence learning: a step size per weight out of 16 bytes of accumulators, E the
+// sum of the D a weight received and A the sum of their |D|) is three launches for the same reason:
+// nt_tc_weights_kernel between the two reads the records and adds each weight's share of D,
+// nt_tc_update_kernel adds to the records (64-bit atomics) and ends like nt_td_update_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -113,8 +117,46 @@ __global__ __launch_bounds__(256) void nt_td_eval_kernel(NtArgs net, const uint4
     ws_act[i] = (uint8_t)c.best;
 }
 
-// TD step, the writing half: the update of the pending after-state, then g2048_env_step with the
-// greedy action and auto-reset at counter c + t, the running score and the carried state
+// The end of a step's last launch, the same for both learners: g2048_env_step of env i with the greedy
+// action and auto-reset at counter c + t, the running score, the finished game's statistics, and the
+// carried state (after, pending)
+__device__ __forceinline__ void nt_step_env(uint4 *boards, uint4 *after, uint8_t *pending, long long *run_score,
+                                            const uint8_t *ws_act, RngArgs rng, uint64_t t, long long *stats,
+                                            uint32_t i) {
+    const uint32_t act = ws_act[i];
+    const bool has_move = act != 0xFFu;
+    const uint32_t a = has_move ? act : 0u;
+    uint4 b = boards[i];
+    uint32_t pts, mx;
+    const uint4 moved = apply_move(b, a, pts, mx);
+    const StepResult res = step_board<G2048_RNG_PHILOX>(b, true, a, nullptr, rng, (int64_t)i, rng_counter(rng) + t,
+                                                        G2048_OPT_AUTO_RESET);
+    long long rs = run_score[i] + (long long)res.pts;
+    const bool done = (res.fl & FLAG_DONE) != 0u;
+    if (done) {
+        if (stats) {
+            __hip_atomic_fetch_add(stats + 0, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(stats + 1, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max(stats + 2, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        rs = 0;
+    }
+    run_score[i] = rs;
+    boards[i] = b;
+    if (has_move) after[i] = moved;
+    pending[i] = (uint8_t)(has_move ? (done ? 2u : 1u) : 0u);
+}
+
+// one add per wave of its updates applied; every lane of the wave calls it
+__device__ __forceinline__ void nt_count_updates(long long *stats, bool updated) {
+    if (stats) {
+        const unsigned long long m = __ballot(updated);
+        if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
+            __hip_atomic_fetch_add(stats + 3, (long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// TD step, the writing half: the update of the pending after-state, then the env step
 template <int K>
 __global__ __launch_bounds__(256) void nt_td_update_kernel(NtArgs net, uint4 *__restrict__ boards,
                                                            uint4 *__restrict__ after, uint8_t *__restrict__ pending,
@@ -130,34 +172,88 @@ __global__ __launch_bounds__(256) void nt_td_update_kernel(NtArgs net, uint4 *__
         const int32_t D = ws_d[i];
         updated = p != 0u;
         if (updated && D != 0) nt_add<K>(net, nt_pack(after[i]), D);
-        const uint32_t act = ws_act[i];
-        const bool has_move = act != 0xFFu;
-        const uint32_t a = has_move ? act : 0u;
-        uint4 b = boards[i];
-        uint32_t pts, mx;
-        const uint4 moved = apply_move(b, a, pts, mx);
-        const StepResult res = step_board<G2048_RNG_PHILOX>(b, true, a, nullptr, rng, (int64_t)i, rng_counter(rng) + t,
-                                                            G2048_OPT_AUTO_RESET);
-        long long rs = run_score[i] + (long long)res.pts;
-        const bool done = (res.fl & FLAG_DONE) != 0u;
-        if (done) {
-            if (stats) {
-                __hip_atomic_fetch_add(stats + 0, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_add(stats + 1, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_max(stats + 2, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            rs = 0;
+        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
+    }
+    nt_count_updates(stats, updated);
+}
+
+// add_i of the TC step: what a weight with the record (E, A) takes of D (include/g2048_ntuple.h)
+// Without a branch on A, so that both words of a record are always used and its gather stays one load.
+__device__ __forceinline__ int32_t nt_tc_share(long long E, unsigned long long A, int32_t D) {
+    const int sh = max(44 - (int)__clzll((long long)A), 0);  // bitlen(A) - 20; __clzll(0) = 64
+    const uint32_t a = (uint32_t)(A >> sh);                   // A != 0: 1 <= a < 2^20
+    const unsigned long long mag = E < 0 ? 0ull - (unsigned long long)E : (unsigned long long)E;
+    const unsigned long long e = min(mag >> sh, (unsigned long long)a);
+    const uint32_t absD = D < 0 ? 0u - (uint32_t)D : (uint32_t)D;
+    const uint32_t q = (uint32_t)(((unsigned long long)absD * e + (a >> 1)) / max(a, 1u));  // below 2^51; q <= |D|
+    return A == 0ull ? D : D < 0 ? -(int32_t)q : (int32_t)q;
+}
+
+// TC step, the launch between the two of the TD step: reads the accumulator records of the pending
+// after-state's 8 T weights (one 16-byte gather each, the 8 of a tuple issued together) and adds each
+// weight's share of D to it.  It writes W only; E and A are only read here and only added to in the
+// next launch, so every lane sees the records before the step's adds.
+typedef long long NtRecord __attribute__((ext_vector_type(2)));  // (E, A): one 16-byte load, not two of 8
+
+template <int K>
+__global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const NtRecord *__restrict__ tc,
+                                                            const uint4 *__restrict__ after,
+                                                            const uint8_t *__restrict__ pending,
+                                                            const int32_t *__restrict__ ws_d, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int32_t D = ws_d[i];
+    if (pending[i] == 0u || D == 0) return;
+    const uint64_t x = nt_pack(after[i]);
+    for (int t = 0; t < net.T; t++) {
+        const size_t base = (size_t)t << (4 * K);
+        uint32_t idx[8];
+        NtRecord r[8];
+#pragma unroll
+        for (int g = 0; g < 8; g++) {
+            idx[g] = nt_index<K>(x, net.cells[8 * t + g]);
+            r[g] = tc[base + idx[g]];
         }
-        run_score[i] = rs;
-        boards[i] = b;
-        if (has_move) after[i] = moved;
-        pending[i] = (uint8_t)(has_move ? (done ? 2u : 1u) : 0u);
+#pragma unroll
+        for (int g = 0; g < 8; g++)
+            __hip_atomic_fetch_add((uint32_t *)net.w + base + idx[g],
+                                   (uint32_t)nt_tc_share(r[g].x, (unsigned long long)r[g].y, D), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (stats) {  // one add per wave of its updates applied
-        const unsigned long long m = __ballot(updated);
-        if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m))
-            __hip_atomic_fetch_add(stats + 3, (long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// TC step, the last launch: D to E and |D| to A of the same 8 T records, then the env step
+template <int K>
+__global__ __launch_bounds__(256) void nt_tc_update_kernel(NtArgs net, unsigned long long *__restrict__ tc,
+                                                           uint4 *__restrict__ boards, uint4 *__restrict__ after,
+                                                           uint8_t *__restrict__ pending,
+                                                           long long *__restrict__ run_score,
+                                                           const int32_t *__restrict__ ws_d,
+                                                           const uint8_t *__restrict__ ws_act, RngArgs rng, uint64_t t,
+                                                           long long *__restrict__ stats, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = i < n;
+    bool updated = false;
+    if (valid) {
+        const uint32_t p = pending[i];
+        const int32_t D = ws_d[i];
+        updated = p != 0u;
+        if (updated && D != 0) {
+            const uint64_t x = nt_pack(after[i]);
+            const unsigned long long dE = (unsigned long long)(long long)D, dA = D < 0 ? 0ull - dE : dE;
+            for (int tt = 0; tt < net.T; tt++) {
+                unsigned long long *rec = tc + ((size_t)tt << (4 * K + 1));
+#pragma unroll
+                for (int g = 0; g < 8; g++) {
+                    const size_t k = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
+                    __hip_atomic_fetch_add(rec + k, dE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(rec + k + 1, dA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
     }
+    nt_count_updates(stats, updated);
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -232,6 +328,50 @@ int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *
                           hipLaunchKernelGGL(nt_td_update_kernel<kK>, grid, block, 0, st, a, (uint4 *)boards,
                                              (uint4 *)after, pending, (long long *)run_score, (const int32_t *)ws_d,
                                              (const uint8_t *)ws_act, r, (uint64_t)t, (long long *)stats, (uint32_t)n));
+        s = launch_status();
+        if (s != G2048_OK) return s;
+    }
+    return G2048_OK;
+}
+
+size_t g2048_ntuple_tc_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
+
+int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes_in) {
+    NtArgs a;
+    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
+    if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
+    if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
+    if (!tc || !aligned16(tc)) return G2048_EINVAL;
+    if (n == 0) return G2048_OK;
+    if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
+        ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||
+        workspace_bytes_in < td_workspace_bytes(n))
+        return G2048_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *ws_d = (int32_t *)workspace;
+    uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
+    const RngArgs r = rng_args(rng);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    for (int64_t t = 0; t < steps; t++) {
+        G2048_NT_DISPATCH(net->tuple_len,
+                          hipLaunchKernelGGL(nt_td_eval_kernel<kK>, grid, block, 0, st, a, (const uint4 *)boards,
+                                             (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
+                                             (uint32_t)n));
+        int s = launch_status();
+        if (s != G2048_OK) return s;
+        G2048_NT_DISPATCH(net->tuple_len,
+                          hipLaunchKernelGGL(nt_tc_weights_kernel<kK>, grid, block, 0, st, a, (const NtRecord *)tc,
+                                             (const uint4 *)after, (const uint8_t *)pending, (const int32_t *)ws_d,
+                                             (uint32_t)n));
+        s = launch_status();
+        if (s != G2048_OK) return s;
+        G2048_NT_DISPATCH(net->tuple_len,
+                          hipLaunchKernelGGL(nt_tc_update_kernel<kK>, grid, block, 0, st, a, (unsigned long long *)tc,
+                                             (uint4 *)boards, (uint4 *)after, pending, (long long *)run_score,
+                                             (const int32_t *)ws_d, (const uint8_t *)ws_act, r, (uint64_t)t,
+                                             (long long *)stats, (uint32_t)n));
         s = launch_status();
         if (s != G2048_OK) return s;
     }

@@ -367,6 +367,32 @@ def ntuple_td(net: NtNet, boards, after, pending, run_score, steps: int, lr_shif
           _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
 
 
+def ntuple_tc_workspace_bytes(n: int) -> int:
+    """0 for an n g2048_ntuple_tc would refuse."""
+    return int(load().g2048_ntuple_tc_workspace_bytes(int(n)))
+
+
+def ntuple_tc(net: NtNet, tc, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
+              workspace=None):
+    """`steps` temporal-coherence steps of the n envs on one net (g2048_ntuple_tc): ntuple_td's arguments and
+    tc, the int64 device tensor [T, 16^K, 2] of the accumulators (E, A) of the net's weights, on the
+    device of boards; workspace: a uint8 device tensor of ntuple_tc_workspace_bytes(n) bytes."""
+    n = boards.shape[0]
+    count = 2 * (net.num_tuples << (4 * net.tuple_len))  # two int64 per weight
+    if tc is None or tc.dtype != torch.int64 or tc.numel() != count or tc.device != boards.device:
+        raise G2048Error(f"ntuple_tc: tc must be int64 with {count} elements on {boards.device}, got "
+                         f"{None if tc is None else (tc.dtype, tc.numel(), tc.device)}")
+    for t, nm, k in ((after, "after", 16 * n), (pending, "pending", n), (run_score, "run_score", n), (stats, "stats", 4)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_tc: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("ntuple_tc: a workspace of ntuple_tc_workspace_bytes(n) bytes is required")
+    _call("g2048_ntuple_tc", _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
+          _dev(boards, torch.int8, "boards"), _dev(after, torch.int8, "after"), _dev(pending, torch.uint8, "pending"),
+          _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), ctypes.byref(rng),
+          _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
+
+
 def preview_points(boards, points4):
     _call("g2048_preview_points", _stream(boards), _dev(boards, torch.int8, "boards"),
           _dev(points4, torch.int32, "points4"), boards.shape[0])

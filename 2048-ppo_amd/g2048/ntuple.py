@@ -5,7 +5,9 @@ NTupleNet: T tuples of K board cells and one int32 table of 16^K weights per tup
 board is the sum of the 8 T weights its tuples index under the 8 symmetries of the square, in points x
 4096.  NTupleTrainer: `envs` games learning in parallel on one net (g2048_ntuple_td): every env plays the
 move of the largest points + value and moves the weights of its previous after-state towards that
-maximum; the updates are integer adds, so a run is reproducible bit for bit.  NTuplePlayer: the greedy
+maximum; the updates are integer adds, so a run is reproducible bit for bit.  With rule="tc" every
+weight sets its own step size from the sums of its past updates (temporal-coherence learning,
+g2048_ntuple_tc), integer too.  NTuplePlayer: the greedy
 player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
 search.py's game loop.
 """
@@ -85,17 +87,28 @@ class NTupleNet:
 class NTupleTrainer:
     """`envs` Philox games keyed by `seed`: the reset at counter 0, TD step s at counter 1 + s.
     lr_shift in 1..30: an update adds delta / 2^lr_shift to each of the 8 T weights; concurrent envs add
-    up on shared weights, so a usable lr_shift grows with envs (10 at 256)."""
+    up on shared weights, so a usable lr_shift grows with envs (10 at 256).
+    rule "td": plain TD(0) (g2048_ntuple_td).  rule "tc": temporal-coherence learning (g2048_ntuple_tc):
+    every weight keeps the signed and the absolute sum of the updates it received (self.tc, int64
+    [T, 16^K, 2], zero at the start: 16 bytes per weight on top of its 4) and takes the share
+    |signed sum| / absolute sum of an update; lr_shift is then the base rate at which a fresh weight
+    starts.  The accumulators belong to the trainer, not to the net: NTupleNet.save keeps the net only,
+    and resuming a TC run from a saved net is out of scope (a new trainer starts from zero accumulators)."""
 
-    def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048):
+    RULES = ("td", "tc")
+
+    def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td"):
         envs, lr_shift = int(envs), int(lr_shift)
         if not 1 <= envs <= MAX_ENVS:
             raise ValueError(f"envs must be in [1, {MAX_ENVS}], got {envs}")
         if not 1 <= lr_shift <= 30:
             raise ValueError(f"lr_shift must be in [1, 30], got {lr_shift}")
-        self.net, self.envs, self.lr_shift, self.seed = net, envs, lr_shift, int(seed)
+        if rule not in self.RULES:
+            raise ValueError(f"rule must be one of {self.RULES}, got {rule!r}")
+        self.net, self.envs, self.lr_shift, self.seed, self.rule = net, envs, lr_shift, int(seed), rule
         self.counter = 0
         self.boards = None
+        self.tc = None
 
     def _start(self):
         d, n = self.net.device, self.envs
@@ -104,7 +117,11 @@ class NTupleTrainer:
         self.pending = torch.zeros(n, dtype=torch.uint8, device=d)
         self.run_score = torch.zeros(n, dtype=torch.int64, device=d)
         self.stats = torch.zeros(4, dtype=torch.int64, device=d)
-        self.workspace = torch.empty(L.ntuple_td_workspace_bytes(n), dtype=torch.uint8, device=d)
+        if self.rule == "tc":
+            self.tc = torch.zeros(*self.net.weights.shape, 2, dtype=torch.int64, device=d)
+            self.workspace = torch.empty(L.ntuple_tc_workspace_bytes(n), dtype=torch.uint8, device=d)
+        else:
+            self.workspace = torch.empty(L.ntuple_td_workspace_bytes(n), dtype=torch.uint8, device=d)
         L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
         self.counter = 1
 
@@ -118,12 +135,26 @@ class NTupleTrainer:
         if self.boards is None:
             self._start()
         self.stats.zero_()
-        L.ntuple_td(self.net.c, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift,
-                    L.make_rng(L.RNG_PHILOX, self.seed, self.counter), self.stats, self.workspace)
+        rng = L.make_rng(L.RNG_PHILOX, self.seed, self.counter)
+        if self.rule == "tc":
+            L.ntuple_tc(self.net.c, self.tc, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift,
+                        rng, self.stats, self.workspace)
+        else:
+            L.ntuple_td(self.net.c, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift, rng,
+                        self.stats, self.workspace)
         self.counter += steps
         games, score_sum, best, updates = self.stats.tolist()
         return {"games": games, "mean_score": score_sum / games if games else 0.0, "max_score": best,
                 "updates": updates, "score_sum": score_sum}
+
+    def accumulators(self):
+        """-> (E, A): views int64 [T, 16^K] of a weight's signed and absolute update sums under rule "tc" (A
+        is unsigned: read its int64 as uint64); None, None before the first train()."""
+        if self.rule != "tc":
+            raise ValueError('only rule "tc" keeps accumulators')
+        if self.tc is None:
+            return None, None
+        return self.tc[..., 0], self.tc[..., 1]
 
 
 class NTuplePlayer(_SearchPlayer):

@@ -391,24 +391,33 @@ def play_expectimax(games: int = typer.Option(100, "--games", "-g"),
 def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD steps of every env"),
                  envs: int = typer.Option(256, "--envs", help="games learning in parallel on the one net"),
                  lr_shift: int = typer.Option(10, "--lr-shift", help="an update adds delta / 2^lr_shift (1..30); "
-                                                                    "raise it with --envs"),
+                                                                    "raise it with --envs.  Under --rule tc the "
+                                                                    "base rate at which a fresh weight starts"),
                  tuples: str = typer.Option("lines-squares-4", "--tuples", help="tuple preset: lines-squares-4, 4x6"),
                  seed: int = typer.Option(0x2048, "--seed"),
                  out: Optional[Path] = typer.Option(None, "--out", help="where to save the net"),
-                 print_frequency: int = typer.Option(1000, "--print-freq", "-p", help="steps between two reports")):
+                 print_frequency: int = typer.Option(1000, "--print-freq", "-p", help="steps between two reports"),
+                 rule: str = typer.Option("td", "--rule", help="td: one step size for every weight; tc: "
+                                                               "temporal-coherence learning, a step size per weight "
+                                                               "from the sums of its past updates")):
     """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
-    reproducible bit for bit.  Prints the games finished and their mean score per interval."""
+    reproducible bit for bit.  Prints the games finished and their mean score per interval.  --rule tc
+    keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, so resuming a TC
+    run from a saved net is out of scope."""
     from g2048.ntuple import PRESETS, NTupleNet, NTupleTrainer
     if tuples not in PRESETS:
         typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
+        raise typer.Exit(1)
+    if rule not in NTupleTrainer.RULES:
+        typer.echo(f"Unknown learning rule: {rule}. Use one of {', '.join(NTupleTrainer.RULES)}.")
         raise typer.Exit(1)
     if not torch.cuda.is_available():
         typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
         raise typer.Exit(1)
     net = NTupleNet(tuples, torch.device("cuda", 0))
-    tr = NTupleTrainer(net, envs, lr_shift, seed)
+    tr = NTupleTrainer(net, envs, lr_shift, seed, rule)
     typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
-               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}")
+               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}, rule {rule}")
     done = 0
     while done < steps:
         k = min(max(print_frequency, 1), steps - done)

@@ -1,10 +1,11 @@
 /*
  * g2048_ntuple.h -- n-tuple network with afterstate TD(0) learning (Szubert & Jaskowski 2014; Yeh et
- * al. 2016) on the 2048 engine of g2048.h: the table-based learner a 2048 agent is compared with.  No
- * reference counterpart.  The conventions are those of g2048.h: device pointers (except the host
- * structs g2048_ntuple_net / g2048_rng, read during the call), asynchronous on `stream`, no allocation
- * and no host synchronisation (hipGraph-capturable), 0 / G2048_EINVAL (nothing enqueued) / a positive
- * hipError_t, n = 0 a no-op.  This text is the specification; tests/ntuple_reference.py restates it.
+ * al. 2016), optionally with temporal-coherence step sizes, on the 2048 engine of g2048.h: the
+ * table-based learner a 2048 agent is compared with.  No reference counterpart.  The conventions are
+ * those of g2048.h: device pointers (except the host structs g2048_ntuple_net / g2048_rng, read during
+ * the call), asynchronous on `stream`, no allocation and no host synchronisation (hipGraph-capturable),
+ * 0 / G2048_EINVAL (nothing enqueued) / a positive hipError_t, n = 0 a no-op.  This text is the
+ * specification; tests/ntuple_reference.py restates it, tests/ntuple_tc_reference.py the TC step.
  *
  * The network.  T tuples of K cells each (cell = 4 row + col) and one table of 16^K int32 weights per
  * tuple.  All values are integers: points x S, S = 2^G2048_NT_FRAC_BITS = 4096.
@@ -40,6 +41,30 @@
  * Range.  The weights WRAP on overflow (two's complement): one weight holds +-2^31 / S = +-2^19
  * points.  Concurrent envs add up on shared weights, so a usable lr_shift grows with n: from zero
  * weights, five 4-tuples and n = 256, lr_shift 9 drove weights to 2^31 while lr_shift 10 learned.
+ *
+ * The TC step (g2048_ntuple_tc): temporal-coherence learning (Beal & Smith 1999; Jaskowski 2018), a step
+ * size per weight instead of the one lr_shift.  Every weight i of the net has an accumulator record
+ * of 16 bytes in the device array tc, int64 [T][16^K][2]: tc[2 i] = E_i, the sum of the D it received
+ * (int64), tc[2 i + 1] = A_i, the sum of their |D| (read as uint64).  Both wrap like the weights;
+ * zero-filled means "never updated".  A weight moves at the rate |E_i| / A_i: one whose errors agree
+ * keeps learning at the full rate, one whose errors cancel slows itself down.
+ * A TC step is the TD step, 1-4, with step 2 replaced: delta and D are computed exactly as there, and
+ * for each of the 8 T weights i that V(after[i]) reads, counted with multiplicity, with E_i and A_i as
+ * they were before this step's adds,
+ *   A_i == 0:  add_i = D
+ *   otherwise: sh = max(bitlen(A_i) - 20, 0),  a = A_i >> sh  (1 <= a < 2^20),
+ *              e = min(|E_i| >> sh, a)         |E_i| the unsigned magnitude: 2^63 for INT64_MIN
+ *              add_i = sign(D) floor((|D| e + (a >> 1)) / a)
+ *   W_i += add_i (int32, wraps),  E_i += D,  A_i += |D|.
+ * Every read of a step (W, E, A) sees the values before that step's adds: the read-before-write rule
+ * of the TD step, extended to the accumulators.  A self-symmetric tuple hits one weight twice: both
+ * hits read the same record, and W, E and A each receive two adds.  An (env, step) with pending != 0
+ * counts as one update applied, as there.  |D| <= 2^30 and e < 2^20, so the numerator is below 2^51 and
+ * the quotient at most |D|; the integer result is the specification, however it is divided.  The min
+ * makes the rule total on any accumulator contents; in a run from zeros |E| <= A holds without it.
+ * With D = 0 nothing changes: no weight, no E, no A.  With every A = 0 the first hit of every weight is
+ * plain TD(0): lr_shift is the base rate at which a fresh weight starts.  All adds are integer adds of
+ * values fixed by the reads, so they commute and a run stays bitwise reproducible.
  *
  * The search (g2048_ntuple_search).  Expectimax with V at the leaves: d = depth in 1..3 moves looked
  * ahead, the root move included; E(s) = the number of empty cells of s; s + t@c = s with exponent t
@@ -113,6 +138,18 @@ size_t g2048_ntuple_td_workspace_bytes(int64_t n);
 int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
                     uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                     const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
+
+/* `steps` TC steps (the TC step, above) of n envs on one net and its accumulators tc, int64 [T][16^K][2]
+   (device, 16-B aligned, read and updated; zero-filled at the start of a run), three launches per step:
+   evaluate (reads W), add to W (reads E and A), add to E and A and step the envs; stream order between
+   them is the read-before-write rule.  Everything else -- the carried state, stats, the workspace (of
+   g2048_ntuple_tc_workspace_bytes(n) bytes), the refusals -- is g2048_ntuple_td's; in addition
+   G2048_EINVAL for a null or misaligned tc. */
+size_t g2048_ntuple_tc_workspace_bytes(int64_t n);
+int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards,
+                    int8_t *after, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                    int32_t lr_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
+                    size_t workspace_bytes);
 
 /* Expectimax search of depth 1..3 with V at the leaves (the search, above) on n boards: q int64 [n][4]
    (16-B aligned, required), leaves int64 [n][4] (nullable, 16-B aligned), legal / best uint8 [n]
