@@ -88,14 +88,28 @@ __device__ __forceinline__ uint32_t fresh_stats(uint32_t p1, uint32_t v1, uint32
 // lines' maximum: a step's only table reads are the records of the board it produces.  A board
 // holding an exponent > 10 takes the SWAR compute path.  Workgroups are persistent over boards, so
 // large N keeps several waves per SIMD with one LDS table per CU.
+// kAddr = how a step forms its line addresses (rollout_step.hpp): the host takes the MFMA form where a
+// SIMD holds one wave (up to 256 threads per workgroup, the benchmark's 65 536 boards among them: the
+// kernel is issue-bound there and the form is 5 % faster) and the VALU form above that (at four waves per
+// SIMD the MFMA form measured 3.5 % slower at 2^20 boards and 9 % slower at 2^22: profiles/r15a).
+template <int kAddr>
 __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ boards, int64_t n, int64_t steps,
                                                            uint4 *__restrict__ tb, uint8_t *__restrict__ ta,
                                                            int32_t *__restrict__ tp, uint32_t *__restrict__ tpot,
                                                            uint8_t *__restrict__ tf, RngArgs rng,
-                                                           uint32_t *__restrict__ ticket = nullptr) {
+                                                           uint32_t *__restrict__ ticket) {
     // kLine11, then kFresh and kFreshLines (the layout is line11_lds.hpp's, the address bounds are rollout_step.hpp's)
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kRolloutLdsWords];
+    // The MFMA's constant operand, loaded once per wave here, where all 64 lanes are active: the
+    // instruction reads its operands in every lane whatever EXEC says, so a fragment written (or
+    // rematerialised) under the board loop's partial EXEC would leave garbage in the rows that belong
+    // to the inactive lanes, for every board of the wave.  The empty asm behind the barrier makes the
+    // registers an asm result -- nothing the compiler can recompute or sink into the loop -- and costs
+    // no instruction; a pin at the use site would cost two v_mov_b64 per step.
+    i32x4 fa{};
+    if constexpr (kAddr != kAddrValu) fa = line_mfma_frag();
     stage_row_table(s_row);
+    if constexpr (kAddr != kAddrValu) asm volatile("" : "+v"(fa));
     const uint64_t ctr0 = rng_counter(rng);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -118,14 +132,14 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         s.D = philox_draw(rng.seed, pair, env, 1u);
         s.ph = philox_start(rng.seed, pair + 1u, env, 1u);
         fresh_prep(s, s_row);
-        refill_lines(s, s_row, s.S >> 24);
+        refill_lines<kAddr>(s, s_row, s.S >> 24, fa);
         // per-lane record addresses, advanced one row (n elements) per step: no array base in an SGPR
         // pair across the loop (the loop's SGPR spills)
         TrajRows tr{tb + li, ta + li, tp + li, tpot + li, tf + li};
         uint64_t left = (uint64_t)steps;  // steps still to run
         if ((ctr0 & 1u) && left > 0u) {  // the launch starts on the second step of a pair
             philox_rounds<0, 5>(s.ph);
-            rollout_step<true, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+            rollout_step<true, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             tr.next(n);
             pair++;
             left--;
@@ -140,17 +154,17 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
             // and without masking its addresses.  The other pair keeps the carried records valid in
             // every lane whose board is <= 2^10, so a wave changes between the two freely.
             if (__all(s.S < ((kFastPairMax + 1u) << 24))) {
-                rollout_step<false, true, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+                rollout_step<false, true, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
                 tr.next(n);
-                rollout_step<true, true, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+                rollout_step<true, true, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             } else {
-                rollout_step<false, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+                rollout_step<false, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
                 tr.next(n);
-                rollout_step<true, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+                rollout_step<true, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             }
             tr.next(n);
         }
-        if (left & 1u) rollout_step<false, false, true>(s, s_row, tr, rng.seed, pair + 2u, env);
+        if (left & 1u) rollout_step<false, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
         boards[i] = s.b;
     }
     if (ticket) {
@@ -204,7 +218,8 @@ static int rollout_launch(g2048_stream_t stream, int8_t *boards, int64_t n, int6
         !aligned16(traj_boards) || ((uintptr_t)traj_pot & 3u) || ((uintptr_t)traj_points & 3u))
         return G2048_EINVAL;
     const PersistentShape sh = persistent_shape(n);
-    hipLaunchKernelGGL(env_rollout_kernel, dim3(sh.grid), dim3(sh.threads), 0, (hipStream_t)stream,
+    const auto kernel = sh.threads <= 256u ? env_rollout_kernel<kAddrMfma> : env_rollout_kernel<kAddrValu>;
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(sh.threads), 0, (hipStream_t)stream,
                        (uint4 *)boards, n, steps, (uint4 *)traj_boards, traj_actions, traj_points, (uint32_t *)traj_pot,
                        traj_flags, rng_args(rng), ticket);
     return launch_status();

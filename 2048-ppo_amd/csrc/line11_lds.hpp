@@ -60,6 +60,110 @@ __device__ __forceinline__ void line11_addrs(const uint4 &b, uint32_t (&ra)[4], 
     ca[2] = (p02 >> 16) << 3;
     ca[3] = (p13 >> 16) << 3;
 }
+
+// The same eight addresses from the matrix pipe: every address is linear in the 16 board bytes, so one
+// v_mfma_i32_32x32x32_i8 with the board as the B operand (lane l already holds its board's 16 bytes in
+// 4 VGPRs, which is one lane's B fragment: nothing moves between lanes) and a constant A operand gives a
+// lane 16 dot products of its own board.  8 x 1331 does not fit int8, so an address comes as two limbs,
+// lo = 8 d0 + 88 d1 (<= 960) and hi = d2 + 11 d3 (<= 120), addr = lo + 968 hi (one v_mad_u32_u24):
+// output q < 8 is the lo limb of line q (rows 0..3 left to right, then columns 0..3 top to bottom, as
+// line11_addrs reads them), output q + 8 its hi limb.
+//   C/D layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), so lane (h, n) receives
+//   the 16 rows m with ((m >> 2) & 1) == h, row m in register q = (m & 3) + 4 (m >> 3).
+//   A: row m lives in lanes (0, m) and (1, m), one half of k each.  Lane (h', m) holds the weights of
+//   output q when ((m >> 2) & 1) == h' and zero otherwise, so the row sums over the boards of lane half
+//   h' only, and register q of every lane is the dot product of the lane's own board with weights q.
+// Of the k-map the scheme needs only that element j of A meets element j of B within a lane half and
+// that the halves do not mix (line_mfma_model; tests/test_gpu_rollout_line_addrs.py checks it on the
+// hardware with every table index through every line).
+// MFMA reads its operands in every lane whatever EXEC says: the A fragment has to be loaded with all 64
+// lanes active and never rewritten under a partial EXEC (env_rollout_kernel loads it at its start).
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+constexpr uint32_t kLineHiScale = 8u * g2048::lut::kLineBase * g2048::lut::kLineBase;  // 968
+// weight of board byte c = 4 row + col in output q
+constexpr int line_mfma_weight(uint32_t q, uint32_t c) {
+    const uint32_t line = q & 7u, r = c >> 2, col = c & 3u;
+    const uint32_t pos = line < 4u ? (r == line ? col : 4u) : (col == line - 4u ? r : 4u);  // the cell's place in the line
+    if (q < 8u) return pos == 0u ? 8 : pos == 1u ? 8 * (int)g2048::lut::kLineBase : 0;
+    return pos == 2u ? 1 : pos == 3u ? (int)g2048::lut::kLineBase : 0;
+}
+struct LineMfmaTable {  // the A fragment of lane l: 16 int8, byte j of dword w pairs with board byte 4 w + j
+    uint32_t a[64][4];
+    constexpr LineMfmaTable() : a() {
+        for (uint32_t l = 0u; l < 64u; l++) {
+            const uint32_t m = l & 31u, q = (m & 3u) + 4u * (m >> 3);
+            if (((m >> 2) & 1u) != (l >> 5)) continue;
+            for (uint32_t c = 0u; c < 16u; c++) a[l][c >> 2] |= ((uint32_t)line_mfma_weight(q, c) & 0xFFu) << (8u * (c & 3u));
+        }
+    }
+};
+// register `reg` of lane (h, n) after the instruction, from the B fragments of lanes (0, n) and (1, n)
+constexpr int32_t line_mfma_model(const LineMfmaTable &t, const uint32_t (&b0)[4], const uint32_t (&b1)[4], uint32_t h, uint32_t reg) {
+    const uint32_t m = (reg & 3u) + 8u * (reg >> 2) + 4u * h;
+    int32_t d = 0;
+    for (uint32_t hh = 0u; hh < 2u; hh++)
+        for (uint32_t j = 0u; j < 16u; j++) {
+            const int32_t av = (int8_t)(t.a[32u * hh + m][j >> 2] >> (8u * (j & 3u)));
+            const int32_t bv = (int8_t)((hh ? b1 : b0)[j >> 2] >> (8u * (j & 3u)));
+            d += av * bv;
+        }
+    return d;
+}
+constexpr bool line_mfma_weights_int8() {
+    for (uint32_t q = 0u; q < 16u; q++)
+        for (uint32_t c = 0u; c < 16u; c++)
+            if (line_mfma_weight(q, c) < 0 || line_mfma_weight(q, c) > 127) return false;
+    return true;
+}
+// every digit 0..10 in every position of every line (digit (k + 3 col + 5 row) mod 11 in cell (row,
+// col)), in either lane half, with another board in the other half
+constexpr bool line_mfma_ok() {
+    const LineMfmaTable t;
+    for (uint32_t k = 0u; k < 11u; k++)
+        for (uint32_t h = 0u; h < 2u; h++) {
+            uint32_t c[16] = {}, mine[4] = {0u, 0u, 0u, 0u}, other[4] = {0u, 0u, 0u, 0u};
+            for (uint32_t i = 0u; i < 16u; i++) {
+                c[i] = (k + 3u * (i & 3u) + 5u * (i >> 2)) % 11u;
+                mine[i >> 2] |= c[i] << (8u * (i & 3u));
+                other[i >> 2] |= ((c[i] + 1u + i) % 11u) << (8u * (i & 3u));
+            }
+            for (uint32_t r = 0u; r < 4u; r++) {
+                const uint32_t lo_r = (uint32_t)line_mfma_model(t, h ? other : mine, h ? mine : other, h, r);
+                const uint32_t hi_r = (uint32_t)line_mfma_model(t, h ? other : mine, h ? mine : other, h, 8u + r);
+                const uint32_t lo_c = (uint32_t)line_mfma_model(t, h ? other : mine, h ? mine : other, h, 4u + r);
+                const uint32_t hi_c = (uint32_t)line_mfma_model(t, h ? other : mine, h ? mine : other, h, 12u + r);
+                if (lo_r > 960u || hi_r > 120u || lo_c > 960u || hi_c > 120u) return false;
+                if (lo_r + kLineHiScale * hi_r != 8u * g2048::lut::line11_index(c[4 * r], c[4 * r + 1], c[4 * r + 2], c[4 * r + 3])) return false;
+                if (lo_c + kLineHiScale * hi_c != 8u * g2048::lut::line11_index(c[r], c[4 + r], c[8 + r], c[12 + r])) return false;
+            }
+        }
+    return true;
+}
+static_assert(line_mfma_weights_int8(), "the MFMA address weights fit int8");
+static_assert(line_mfma_ok(), "the MFMA address model against line11_index");
+__device__ const LineMfmaTable kLineMfmaA __attribute__((aligned(16))) = LineMfmaTable();
+// this lane's A fragment; call it with all 64 lanes of the wave active
+__device__ __forceinline__ i32x4 line_mfma_frag() {
+    return *reinterpret_cast<const i32x4 *>(kLineMfmaA.a[threadIdx.x & 63u]);
+}
+// the 16 limbs of a board (q < 8 lo, q + 8 hi) and the addresses from them
+__device__ __forceinline__ i32x16 line11_limbs_mfma(const uint4 &b, const i32x4 &fa) {
+    const i32x4 bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w};
+    const i32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, bv, zero, 0, 0, 0);
+}
+__device__ __forceinline__ void line11_addrs_from_limbs(const i32x16 &d, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        ra[i] = __umul24((uint32_t)d[8 + i], kLineHiScale) + (uint32_t)d[i];
+        ca[i] = __umul24((uint32_t)d[12 + i], kLineHiScale) + (uint32_t)d[4 + i];
+    }
+}
+// line11_addrs' interface plus the A fragment
+__device__ __forceinline__ void line11_addrs_mfma(const uint4 &b, const i32x4 &fa, uint32_t (&ra)[4], uint32_t (&ca)[4]) {
+    line11_addrs_from_limbs(line11_limbs_mfma(b, fa), ra, ca);
+}
 __device__ __forceinline__ uint2 lds_rec(const uint32_t *tab, uint32_t addr) {
     return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(tab) + addr);
 }

@@ -117,13 +117,22 @@ __device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__r
     s.C[3] = lds_rec(tab, la.w >> 16);
 }
 
+// How a step (and refill_lines) turns a board into the eight line addresses: line11_addrs (packed-u16
+// VALU, about 28 instructions) or line11_addrs_mfma (one int8 MFMA against the wave's A fragment `fa`,
+// which the kernel loads at its start with every lane active, and 8 multiply-adds).  The MFMA form is
+// env_rollout_kernel's where a SIMD holds one wave (5 % faster there, slower at four waves per SIMD);
+// mc_search_kernel keeps the VALU form, the default.
+constexpr int kAddrValu = 0, kAddrMfma = 1;
+
 // the records of the current board's lines from the board itself (launch start; the steps keep them
 // up to date from then on).  A lane whose board holds an exponent > 10 (mx = its maximum) reads the
 // empty line's.
-__device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__restrict__ tab, uint32_t mx) {
+template <int kAddr = kAddrValu>
+__device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__restrict__ tab, uint32_t mx, const i32x4 &fa = i32x4{}) {
     const uint4 ab = sel4(mx > kMaxLineDigit, make_uint4(0u, 0u, 0u, 0u), s.b);
     uint32_t ra[4], ca[4];
-    line11_addrs(ab, ra, ca);
+    if constexpr (kAddr == kAddrValu) line11_addrs(ab, ra, ca);
+    else line11_addrs_mfma(ab, fa, ra, ca);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         s.R[i] = lds_rec(tab, ra[i]);
@@ -155,9 +164,9 @@ struct TrajRows {  // this lane's element of row t of each time-major trajectory
 // step (no SWAR fallback, no address masking).  One 32-bit word u per step: action
 // k = floor(u * nlegal / 2^32); the low word r of that product (uniform given k) picks the spawn cell
 // and value.  kTraj = false never touches tr.
-template <bool kOdd, bool kSmall, bool kTraj>
+template <bool kOdd, bool kSmall, bool kTraj, int kAddr = kAddrValu>
 __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__restrict__ tab, const TrajRows &tr,
-                                             uint64_t seed, uint64_t next_pair, uint32_t env) {
+                                             uint64_t seed, uint64_t next_pair, uint32_t env, const i32x4 &fa = i32x4{}) {
     // kTraj: explicit waits for every LDS load in flight (a reset's reload, fresh_prep's two reads), so
     // that the wait-count pass sees an empty queue behind them.  Where the fast pair joins the path
     // that leaves the other pair the pass merges that pair's pending reloads into the fast pair's state
@@ -208,7 +217,8 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     // record needs, it has to be switched off by hand: first_cell_eq's v_ffbl_b32 is written-out asm,
     // which stays in the IR up to instruction selection when unused and moves the schedule of the
     // kTraj = false step (119 instead of 117 VGPRs, + 0.8 % on the search: profiles/r09a/time_mc_search_ab.log)
-    const uint32_t pos_a = kTraj ? first_cell_eq(rm, Ma) : 0u;
+    uint32_t pos_a = 0u;
+    if constexpr (kTraj && kAddr == kAddrValu) pos_a = first_cell_eq(rm, Ma);
     // spawn on the k-th empty cell (row-major), k = floor(r * empties / 2^32), value 1 if the low
     // word of r * empties is below 0.9 * 2^32 (given k that low word is uniform to within
     // empties / 2^32); the row from the prefix counts of empties, the column inside the row likewise
@@ -279,7 +289,17 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
         va = big ? 0u : v;
     }
     uint32_t ra[4], ca[4];
-    line11_addrs(ab, ra, ca);
+    if constexpr (kAddr == kAddrValu) {
+        line11_addrs(ab, ra, ca);
+    } else {
+        // The MFMA's result is ready 12 issue slots after it issues, and the compiler pads what the
+        // schedule leaves of them with s_nop.  first_cell_eq needs the moved board and its maximum only,
+        // so in source order behind the MFMA its ~20 instructions fill that shadow (the multipliers
+        // below follow them): no s_nop is left in the fast pair (profiles/r15a, arm m1a).
+        const i32x16 limbs = line11_limbs_mfma(ab, fa);
+        if constexpr (kTraj) pos_a = first_cell_eq(rm, Ma);
+        line11_addrs_from_limbs(limbs, ra, ca);
+    }
     constexpr uint64_t kW11 = 0x299803C800580008ull;  // 8 x {1, 11, 121, 1331}
     const uint32_t rq = kTraj ? pick4m(mr0, mr1, ra[0], ra[1], ra[2], ra[3]) : r3 ? ra[3] : r2 ? ra[2] : r1 ? ra[1] : ra[0];
     const uint32_t cq = kTraj ? pick4m(mc0, mc1, ca[0], ca[1], ca[2], ca[3]) : c3 ? ca[3] : c2 ? ca[2] : c1 ? ca[1] : ca[0];

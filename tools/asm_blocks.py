@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction counts of env_rollout_kernel from its assembly (make asm):
 python3 tools/asm_blocks.py /tmp/env_rollout.s [min_valu]
+(the first env_rollout_kernel instantiation of the file: kAddrMfma's; blocks(path, "env_rollout_kernelILi0E")
+reads the VALU-address one)
 
 One line per block: label, VALU, of which v_cndmask, LDS reads, scratch_* instructions,
 v_readlane / v_writelane, s_waitcnt lgkmcnt, and the branch targets, so the inner loop's header, its two
