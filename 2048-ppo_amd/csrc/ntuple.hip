@@ -15,6 +15,8 @@
 // sum of the D a weight received and A the sum of their |D|) is three launches for the same reason:
 // nt_tc_weights_kernel between the two reads the records and adds each weight's share of D,
 // nt_tc_update_kernel adds to the records (64-bit atomics) and ends like nt_td_update_kernel.
+// The lambda step (g2048_ntuple_lambda, lambda = 2^-s) has the same launches with writing kernels of its
+// own (nt_lambda_*): they also add D >> k s to the after-state k moves older, kept per env in hist.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -256,6 +258,160 @@ __global__ __launch_bounds__(256) void nt_tc_update_kernel(NtArgs net, unsigned 
     nt_count_updates(stats, updated);
 }
 
+// ---- the lambda step (g2048_ntuple_lambda): the D of after[i] also goes, shifted right by k s, to the
+// after-state k moves older of the same game, k = 1 .. hist_len[i] <= h, out of hist [h][n] boards.
+// The reading launch is nt_td_eval_kernel; the writing launches are the three below, one lane per env,
+// k the outer loop.  A lane loads its h rows of hist once, before any store, and only the step's last
+// launch moves them on, after its adds.
+
+constexpr int kMaxTrace = G2048_NT_MAX_TRACE;
+
+struct NtTrace {
+    uint64_t x[kMaxTrace + 1];  // s_0 = after[i], s_k = hist[k - 1][i], packed
+    uint4 rows[kMaxTrace];      // hist[k][i] as loaded
+    uint4 after;
+    uint32_t len;               // hist_len[i], at most h
+};
+
+// rows at or past h are never read from memory; rows in len .. h - 1 are, and are not used
+__device__ __forceinline__ NtTrace nt_trace_load(const uint4 *after, const uint4 *hist, const uint8_t *hist_len, int h,
+                                                 uint32_t n, uint32_t i) {
+    NtTrace tr;
+    tr.after = after[i];
+    tr.x[0] = nt_pack(tr.after);
+    tr.len = h > 0 ? min((uint32_t)hist_len[i], (uint32_t)h) : 0u;
+#pragma unroll
+    for (int k = 0; k < kMaxTrace; k++) {
+        tr.rows[k] = k < h ? hist[(size_t)k * n + i] : make_uint4(0u, 0u, 0u, 0u);
+        tr.x[k + 1] = nt_pack(tr.rows[k]);
+    }
+    return tr;
+}
+
+// D_k = sign(D) (|D| >> k s): rounds towards zero, symmetrically; k s <= 28
+__device__ __forceinline__ int32_t nt_decay(int32_t D, int ks) {
+    const uint32_t m = (D < 0 ? 0u - (uint32_t)D : (uint32_t)D) >> ks;
+    return D < 0 ? -(int32_t)m : (int32_t)m;
+}
+
+// Step 4 of the lambda step, before nt_step_env overwrites after[i]: the history moves on by the old
+// after[i] when that one waited inside its game (p == 1) and a move follows it; otherwise it empties.
+__device__ __forceinline__ void nt_trace_store(const NtTrace &tr, uint4 *hist, uint8_t *hist_len, int h, uint32_t p,
+                                               bool has_move, uint32_t n, uint32_t i) {
+    if (h <= 0) return;
+    const bool push = has_move && p == 1u;
+    const uint32_t len = push ? min(tr.len + 1u, (uint32_t)h) : 0u;
+    if (push) {
+#pragma unroll
+        for (int k = kMaxTrace - 1; k >= 1; k--)
+            if ((uint32_t)k < len) hist[(size_t)k * n + i] = tr.rows[k - 1];
+        hist[i] = tr.after;
+    }
+    hist_len[i] = (uint8_t)len;
+}
+
+// TD(lambda), the writing half: D_k to the 8 T weights of s_k, then the history and the env step
+template <int K>
+__global__ __launch_bounds__(256) void nt_lambda_td_update_kernel(
+    NtArgs net, uint4 *__restrict__ boards, uint4 *__restrict__ after, uint4 *__restrict__ hist,
+    uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending, long long *__restrict__ run_score,
+    const int32_t *__restrict__ ws_d, const uint8_t *__restrict__ ws_act, int h, int s, RngArgs rng, uint64_t t,
+    long long *__restrict__ stats, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = i < n;
+    bool updated = false;
+    if (valid) {
+        const uint32_t p = pending[i];
+        const int32_t D = ws_d[i];
+        const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
+        updated = p != 0u;
+        if (updated) {
+#pragma unroll
+            for (int k = 0; k <= kMaxTrace; k++) {
+                const int32_t Dk = nt_decay(D, k * s);
+                if ((uint32_t)k <= tr.len && Dk != 0) nt_add<K>(net, tr.x[k], Dk);
+            }
+        }
+        nt_trace_store(tr, hist, hist_len, h, p, ws_act[i] != 0xFFu, n, i);
+        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
+    }
+    nt_count_updates(stats, updated);
+}
+
+// TC(lambda), the launch between: per (k, tuple) the 8 records of s_k are gathered together and each
+// weight takes its share of D_k.  hist is only read here.
+template <int K>
+__global__ __launch_bounds__(256) void nt_lambda_tc_weights_kernel(
+    NtArgs net, const NtRecord *__restrict__ tc, const uint4 *__restrict__ after, const uint4 *__restrict__ hist,
+    const uint8_t *__restrict__ hist_len, const uint8_t *__restrict__ pending, const int32_t *__restrict__ ws_d, int h,
+    int s, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int32_t D = ws_d[i];
+    if (pending[i] == 0u || D == 0) return;
+    const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
+#pragma unroll
+    for (int k = 0; k <= kMaxTrace; k++) {
+        const int32_t Dk = nt_decay(D, k * s);
+        if ((uint32_t)k > tr.len || Dk == 0) continue;
+        const uint64_t x = tr.x[k];
+        for (int t = 0; t < net.T; t++) {
+            const size_t base = (size_t)t << (4 * K);
+            uint32_t idx[8];
+            NtRecord r[8];
+#pragma unroll
+            for (int g = 0; g < 8; g++) {
+                idx[g] = nt_index<K>(x, net.cells[8 * t + g]);
+                r[g] = tc[base + idx[g]];
+            }
+#pragma unroll
+            for (int g = 0; g < 8; g++)
+                __hip_atomic_fetch_add((uint32_t *)net.w + base + idx[g],
+                                       (uint32_t)nt_tc_share(r[g].x, (unsigned long long)r[g].y, Dk), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// TC(lambda), the last launch: D_k to E and |D_k| to A of the records of s_k, then as the TD(lambda) one
+template <int K>
+__global__ __launch_bounds__(256) void nt_lambda_tc_update_kernel(
+    NtArgs net, unsigned long long *__restrict__ tc, uint4 *__restrict__ boards, uint4 *__restrict__ after,
+    uint4 *__restrict__ hist, uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending,
+    long long *__restrict__ run_score, const int32_t *__restrict__ ws_d, const uint8_t *__restrict__ ws_act, int h, int s,
+    RngArgs rng, uint64_t t, long long *__restrict__ stats, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = i < n;
+    bool updated = false;
+    if (valid) {
+        const uint32_t p = pending[i];
+        const int32_t D = ws_d[i];
+        const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
+        updated = p != 0u;
+        if (updated) {
+#pragma unroll
+            for (int k = 0; k <= kMaxTrace; k++) {
+                const int32_t Dk = nt_decay(D, k * s);
+                if ((uint32_t)k > tr.len || Dk == 0) continue;
+                const uint64_t x = tr.x[k];
+                const unsigned long long dE = (unsigned long long)(long long)Dk, dA = Dk < 0 ? 0ull - dE : dE;
+                for (int tt = 0; tt < net.T; tt++) {
+                    unsigned long long *rec = tc + ((size_t)tt << (4 * K + 1));
+#pragma unroll
+                    for (int g = 0; g < 8; g++) {
+                        const size_t j = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
+                        __hip_atomic_fetch_add(rec + j, dE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_add(rec + j + 1, dA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+        }
+        nt_trace_store(tr, hist, hist_len, h, p, ws_act[i] != 0xFFu, n, i);
+        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
+    }
+    nt_count_updates(stats, updated);
+}
+
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 size_t td_workspace_bytes(int64_t n) { return align16((size_t)n * 4) + align16((size_t)n); }
 
@@ -372,6 +528,65 @@ int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t 
                                              (uint4 *)boards, (uint4 *)after, pending, (long long *)run_score,
                                              (const int32_t *)ws_d, (const uint8_t *)ws_act, r, (uint64_t)t,
                                              (long long *)stats, (uint32_t)n));
+        s = launch_status();
+        if (s != G2048_OK) return s;
+    }
+    return G2048_OK;
+}
+
+size_t g2048_ntuple_lambda_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
+
+int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+                        int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                        int32_t lr_shift, int32_t trace_len, int32_t lambda_shift, const g2048_rng *rng, int64_t *stats,
+                        void *workspace, size_t workspace_bytes_in) {
+    NtArgs a;
+    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
+    if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
+    if (trace_len < 0 || trace_len > G2048_NT_MAX_TRACE || lambda_shift < 1 || lambda_shift > G2048_NT_MAX_LAMBDA_SHIFT)
+        return G2048_EINVAL;
+    if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
+    if (!aligned16(tc)) return G2048_EINVAL;
+    if (n == 0) return G2048_OK;
+    if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
+        ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||
+        workspace_bytes_in < td_workspace_bytes(n))
+        return G2048_EINVAL;
+    if (trace_len > 0 && (!hist || !aligned16(hist) || !hist_len)) return G2048_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    int32_t *ws_d = (int32_t *)workspace;
+    uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
+    const RngArgs r = rng_args(rng);
+    const int h = trace_len, ls = lambda_shift;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    for (int64_t t = 0; t < steps; t++) {
+        G2048_NT_DISPATCH(net->tuple_len,
+                          hipLaunchKernelGGL(nt_td_eval_kernel<kK>, grid, block, 0, st, a, (const uint4 *)boards,
+                                             (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
+                                             (uint32_t)n));
+        int s = launch_status();
+        if (s != G2048_OK) return s;
+        if (tc) {
+            G2048_NT_DISPATCH(net->tuple_len,
+                              hipLaunchKernelGGL(nt_lambda_tc_weights_kernel<kK>, grid, block, 0, st, a,
+                                                 (const NtRecord *)tc, (const uint4 *)after, (const uint4 *)hist,
+                                                 (const uint8_t *)hist_len, (const uint8_t *)pending,
+                                                 (const int32_t *)ws_d, h, ls, (uint32_t)n));
+            s = launch_status();
+            if (s != G2048_OK) return s;
+            G2048_NT_DISPATCH(net->tuple_len,
+                              hipLaunchKernelGGL(nt_lambda_tc_update_kernel<kK>, grid, block, 0, st, a,
+                                                 (unsigned long long *)tc, (uint4 *)boards, (uint4 *)after, (uint4 *)hist,
+                                                 hist_len, pending, (long long *)run_score, (const int32_t *)ws_d,
+                                                 (const uint8_t *)ws_act, h, ls, r, (uint64_t)t, (long long *)stats,
+                                                 (uint32_t)n));
+        } else {
+            G2048_NT_DISPATCH(net->tuple_len,
+                              hipLaunchKernelGGL(nt_lambda_td_update_kernel<kK>, grid, block, 0, st, a, (uint4 *)boards,
+                                                 (uint4 *)after, (uint4 *)hist, hist_len, pending, (long long *)run_score,
+                                                 (const int32_t *)ws_d, (const uint8_t *)ws_act, h, ls, r, (uint64_t)t,
+                                                 (long long *)stats, (uint32_t)n));
+        }
         s = launch_status();
         if (s != G2048_OK) return s;
     }

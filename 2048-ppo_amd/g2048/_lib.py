@@ -393,6 +393,39 @@ def ntuple_tc(net: NtNet, tc, boards, after, pending, run_score, steps: int, lr_
           _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
 
 
+def ntuple_lambda_workspace_bytes(n: int) -> int:
+    """0 for an n g2048_ntuple_lambda would refuse."""
+    return int(load().g2048_ntuple_lambda_workspace_bytes(int(n)))
+
+
+def ntuple_lambda(net: NtNet, tc, boards, after, hist, hist_len, pending, run_score, steps: int, lr_shift: int,
+                  trace_len: int, lambda_shift: int, rng: Rng, stats=None, workspace=None):
+    """`steps` TD(lambda) (tc None) or TC(lambda) steps of the n envs on one net (g2048_ntuple_lambda), lambda =
+    2^-lambda_shift over a trace of trace_len after-states: ntuple_td's arguments, tc as ntuple_tc's or None,
+    and the carried history hist int8 [trace_len, n, 16] / hist_len uint8 [n] (both may be None with
+    trace_len 0); workspace: a uint8 device tensor of ntuple_lambda_workspace_bytes(n) bytes."""
+    n, trace_len = boards.shape[0], int(trace_len)
+    if tc is not None:
+        count = 2 * (net.num_tuples << (4 * net.tuple_len))  # two int64 per weight
+        if tc.dtype != torch.int64 or tc.numel() != count or tc.device != boards.device:
+            raise G2048Error(f"ntuple_lambda: tc must be int64 with {count} elements on {boards.device}, got "
+                             f"{(tc.dtype, tc.numel(), tc.device)}")
+    if trace_len > 0 and (hist is None or hist_len is None):
+        raise G2048Error(f"ntuple_lambda: trace_len {trace_len} needs hist and hist_len")
+    for t, nm, k in ((after, "after", 16 * n), (hist, "hist", 16 * n * max(trace_len, 0)), (hist_len, "hist_len", n),
+                     (pending, "pending", n), (run_score, "run_score", n), (stats, "stats", 4)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_lambda: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("ntuple_lambda: a workspace of ntuple_lambda_workspace_bytes(n) bytes is required")
+    _call("g2048_ntuple_lambda", _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
+          _dev(boards, torch.int8, "boards"), _dev(after, torch.int8, "after"), _dev(hist, torch.int8, "hist"),
+          _dev(hist_len, torch.uint8, "hist_len"), _dev(pending, torch.uint8, "pending"),
+          _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), trace_len, int(lambda_shift),
+          ctypes.byref(rng), _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"),
+          workspace.numel())
+
+
 def preview_points(boards, points4):
     _call("g2048_preview_points", _stream(boards), _dev(boards, torch.int8, "boards"),
           _dev(points4, torch.int32, "points4"), boards.shape[0])

@@ -7,7 +7,9 @@ board is the sum of the 8 T weights its tuples index under the 8 symmetries of t
 move of the largest points + value and moves the weights of its previous after-state towards that
 maximum; the updates are integer adds, so a run is reproducible bit for bit.  With rule="tc" every
 weight sets its own step size from the sums of its past updates (temporal-coherence learning,
-g2048_ntuple_tc), integer too.  NTuplePlayer: the greedy
+g2048_ntuple_tc), integer too.  With trace_len > 0 the error of an after-state is also passed back, halved
+(or shifted by lambda_shift) per move, to the trace_len after-states before it: TD(lambda) / TC(lambda) with
+lambda = 2^-lambda_shift (g2048_ntuple_lambda).  NTuplePlayer: the greedy
 player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
 search.py's game loop.
 """
@@ -26,6 +28,7 @@ PRESETS = {
 MAX_TUPLES, MAX_LEN, FRAC_BITS = L.NT_MAX_TUPLES, L.NT_MAX_LEN, L.NT_FRAC_BITS
 MAX_ENVS = (1 << 28) - 1
 MAX_SEARCH_DEPTH = 3
+MAX_TRACE, MAX_LAMBDA_SHIFT = L.NT_MAX_TRACE, L.NT_MAX_LAMBDA_SHIFT
 
 
 def _check_cells(cells) -> list[list[int]]:
@@ -93,22 +96,34 @@ class NTupleTrainer:
     [T, 16^K, 2], zero at the start: 16 bytes per weight on top of its 4) and takes the share
     |signed sum| / absolute sum of an update; lr_shift is then the base rate at which a fresh weight
     starts.  The accumulators belong to the trainer, not to the net: NTupleNet.save keeps the net only,
-    and resuming a TC run from a saved net is out of scope (a new trainer starts from zero accumulators)."""
+    and resuming a TC run from a saved net is out of scope (a new trainer starts from zero accumulators).
+    trace_len in 0..4, lambda_shift in 1..7: with trace_len > 0 either rule runs as g2048_ntuple_lambda, and
+    an update's D is also applied, shifted right by k lambda_shift (towards zero), to the after-state k
+    moves older of the same game, k = 1..trace_len (self.hist int8 [trace_len, envs, 16], self.hist_len
+    uint8 [envs]); a game's end reaches the trace of that game, and a new game starts an empty one.
+    trace_len 0 is exactly the calls above, whatever lambda_shift is."""
 
     RULES = ("td", "tc")
 
-    def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td"):
-        envs, lr_shift = int(envs), int(lr_shift)
+    def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td",
+                 trace_len: int = 0, lambda_shift: int = 1):
+        envs, lr_shift, trace_len, lambda_shift = int(envs), int(lr_shift), int(trace_len), int(lambda_shift)
         if not 1 <= envs <= MAX_ENVS:
             raise ValueError(f"envs must be in [1, {MAX_ENVS}], got {envs}")
         if not 1 <= lr_shift <= 30:
             raise ValueError(f"lr_shift must be in [1, 30], got {lr_shift}")
         if rule not in self.RULES:
             raise ValueError(f"rule must be one of {self.RULES}, got {rule!r}")
+        if not 0 <= trace_len <= MAX_TRACE:
+            raise ValueError(f"trace_len must be in [0, {MAX_TRACE}], got {trace_len}")
+        if not 1 <= lambda_shift <= MAX_LAMBDA_SHIFT:
+            raise ValueError(f"lambda_shift must be in [1, {MAX_LAMBDA_SHIFT}], got {lambda_shift}")
         self.net, self.envs, self.lr_shift, self.seed, self.rule = net, envs, lr_shift, int(seed), rule
+        self.trace_len, self.lambda_shift = trace_len, lambda_shift
         self.counter = 0
         self.boards = None
         self.tc = None
+        self.hist = self.hist_len = None
 
     def _start(self):
         d, n = self.net.device, self.envs
@@ -119,9 +134,13 @@ class NTupleTrainer:
         self.stats = torch.zeros(4, dtype=torch.int64, device=d)
         if self.rule == "tc":
             self.tc = torch.zeros(*self.net.weights.shape, 2, dtype=torch.int64, device=d)
-            self.workspace = torch.empty(L.ntuple_tc_workspace_bytes(n), dtype=torch.uint8, device=d)
+        if self.trace_len > 0:
+            self.hist = torch.zeros(self.trace_len, n, 16, dtype=torch.int8, device=d)
+            self.hist_len = torch.zeros(n, dtype=torch.uint8, device=d)
+            nbytes = L.ntuple_lambda_workspace_bytes(n)
         else:
-            self.workspace = torch.empty(L.ntuple_td_workspace_bytes(n), dtype=torch.uint8, device=d)
+            nbytes = L.ntuple_tc_workspace_bytes(n) if self.rule == "tc" else L.ntuple_td_workspace_bytes(n)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=d)
         L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
         self.counter = 1
 
@@ -136,7 +155,11 @@ class NTupleTrainer:
             self._start()
         self.stats.zero_()
         rng = L.make_rng(L.RNG_PHILOX, self.seed, self.counter)
-        if self.rule == "tc":
+        if self.trace_len > 0:
+            L.ntuple_lambda(self.net.c, self.tc, self.boards, self.after, self.hist, self.hist_len, self.pending,
+                            self.run_score, steps, self.lr_shift, self.trace_len, self.lambda_shift, rng, self.stats,
+                            self.workspace)
+        elif self.rule == "tc":
             L.ntuple_tc(self.net.c, self.tc, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift,
                         rng, self.stats, self.workspace)
         else:

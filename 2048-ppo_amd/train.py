@@ -399,25 +399,39 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
                  print_frequency: int = typer.Option(1000, "--print-freq", "-p", help="steps between two reports"),
                  rule: str = typer.Option("td", "--rule", help="td: one step size for every weight; tc: "
                                                                "temporal-coherence learning, a step size per weight "
-                                                               "from the sums of its past updates")):
+                                                               "from the sums of its past updates"),
+                 trace: int = typer.Option(0, "--trace", help="after-states of the same game that an update also "
+                                                              "reaches, 0..4: TD(lambda) / TC(lambda) with a "
+                                                              "truncated trace; 0: TD(0) / TC"),
+                 lambda_shift: int = typer.Option(1, "--lambda-shift", help="lambda = 2^-S, S in 1..7: the update "
+                                                                            "of the after-state k moves older is "
+                                                                            "shifted right by k S")):
     """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
     reproducible bit for bit.  Prints the games finished and their mean score per interval.  --rule tc
     keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, so resuming a TC
-    run from a saved net is out of scope."""
-    from g2048.ntuple import PRESETS, NTupleNet, NTupleTrainer
+    run from a saved net is out of scope.  --trace H passes every error back along the last H
+    after-states of its game, decayed by lambda = 2^-S (--lambda-shift S), under either rule."""
+    from g2048.ntuple import MAX_LAMBDA_SHIFT, MAX_TRACE, PRESETS, NTupleNet, NTupleTrainer
     if tuples not in PRESETS:
         typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
         raise typer.Exit(1)
     if rule not in NTupleTrainer.RULES:
         typer.echo(f"Unknown learning rule: {rule}. Use one of {', '.join(NTupleTrainer.RULES)}.")
         raise typer.Exit(1)
+    if not 0 <= trace <= MAX_TRACE:
+        typer.echo(f"Error: --trace must be in 0..{MAX_TRACE}, got {trace}")
+        raise typer.Exit(1)
+    if not 1 <= lambda_shift <= MAX_LAMBDA_SHIFT:
+        typer.echo(f"Error: --lambda-shift must be in 1..{MAX_LAMBDA_SHIFT}, got {lambda_shift}")
+        raise typer.Exit(1)
     if not torch.cuda.is_available():
         typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
         raise typer.Exit(1)
     net = NTupleNet(tuples, torch.device("cuda", 0))
-    tr = NTupleTrainer(net, envs, lr_shift, seed, rule)
+    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift)
     typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
-               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}, rule {rule}")
+               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}, trace {trace}, "
+               f"lambda_shift {lambda_shift}, rule {rule}")
     done = 0
     while done < steps:
         k = min(max(print_frequency, 1), steps - done)

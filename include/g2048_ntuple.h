@@ -5,7 +5,8 @@
  * those of g2048.h: device pointers (except the host structs g2048_ntuple_net / g2048_rng, read during
  * the call), asynchronous on `stream`, no allocation and no host synchronisation (hipGraph-capturable),
  * 0 / G2048_EINVAL (nothing enqueued) / a positive hipError_t, n = 0 a no-op.  This text is the
- * specification; tests/ntuple_reference.py restates it, tests/ntuple_tc_reference.py the TC step.
+ * specification; tests/ntuple_reference.py restates it, tests/ntuple_tc_reference.py the TC step,
+ * tests/ntuple_lambda_reference.py the lambda step.
  *
  * The network.  T tuples of K cells each (cell = 4 row + col) and one table of 16^K int32 weights per
  * tuple.  All values are integers: points x S, S = 2^G2048_NT_FRAC_BITS = 4096.
@@ -66,6 +67,41 @@
  * plain TD(0): lr_shift is the base rate at which a fresh weight starts.  All adds are integer adds of
  * values fixed by the reads, so they commute and a run stays bitwise reproducible.
  *
+ * The lambda step (g2048_ntuple_lambda): TD(lambda) and TC(lambda) with a truncated eligibility trace
+ * (Yeh et al. 2016; Jaskowski 2018) and lambda = 2^-s, s = lambda_shift in 1..G2048_NT_MAX_LAMBDA_SHIFT,
+ * so that the decay is a shift and every update stays an integer add.  The error of after[i] is also
+ * passed back to the h = trace_len <= G2048_NT_MAX_TRACE after-states before it in the same game.
+ * Carried beside after / pending:
+ *   hist      int8 [h][n][16] (device, 16-B aligned): hist[k][i] is the after-state of env i that is
+ *             k + 1 moves older than after[i], in the same game
+ *   hist_len  uint8 [n]: how many of them are valid, 0..h; zero-filled at the start
+ * The lambda step is the TD step 1-4 with steps 2 and 4 extended; p = pending[i] as read at the start
+ * of the step.  Steps 1 and 3 are unchanged.
+ *   2. if p != 0: delta and D exactly as in the TD step (the same rounding shift by lr_shift, the same
+ *      clamp to +-2^30).  For k = 0 .. hist_len[i]:
+ *        D_k = sign(D) (|D| >> k s)          D_0 = D; the decay rounds towards zero, symmetrically
+ *        s_0 = after[i],  s_k = hist[k - 1][i]
+ *      and for every k with D_k != 0 the update of the chosen rule is applied to each of the 8 T weights
+ *      that V(s_k) reads, counted with multiplicity, with D_k in the place of D:
+ *        rule TD:  W += D_k
+ *        rule TC:  add_i, E_i += D_k and A_i += |D_k| exactly as the TC step defines them
+ *      One weight may be hit from several k and several envs in one step: all those hits read W, E and
+ *      A as they were before this step's adds.  Such an (env, step) still counts as one update applied.
+ *   4. with a legal move and p == 1: hist[k][i] = hist[k - 1][i] for k = h - 1 .. 1, hist[0][i] = the old
+ *      after[i], hist_len[i] = min(hist_len[i] + 1, h).  With a legal move and p != 1 (nothing was
+ *      waiting, or after[i] ended its game), and without a legal move: hist_len[i] = 0.  Then after /
+ *      pending are set as in the TD step.
+ * So a terminal update (p == 2, target 0) still reaches the history of the game that ended, and the
+ * first after-state of the next game starts with an empty history.  Rows of hist at or beyond
+ * hist_len[i] hold nothing: they are neither used nor kept.
+ * Bounds.  k s <= 4 x 7 = 28, so the shift is always defined; |D_k| <= |D| <= 2^30, so the TC numerator
+ * bound holds unchanged.  With h = 0 the lambda step is the TD step (or the TC step) bit for bit.  The
+ * adds are still integer adds of values fixed by the reads: a run stays bitwise reproducible.
+ * Range.  A trace adds up to 1 + 2^-s + .. + 2^-hs of D to weights that consecutive after-states share,
+ * so under rule TD a usable lr_shift grows with h as it grows with n: from zero weights, five 4-tuples,
+ * n = 256, h = 3 and s = 1, lr_shift 10 collapsed (mean score near 1 000) while lr_shift 11 learned; rule
+ * TC learned at lr_shift 10 with and without the trace.
+ *
  * The search (g2048_ntuple_search).  Expectimax with V at the leaves: d = depth in 1..3 moves looked
  * ahead, the root move included; E(s) = the number of empty cells of s; s + t@c = s with exponent t
  * put on its empty cell c.  All values are int64 in points x S.
@@ -100,6 +136,8 @@ extern "C" {
 #define G2048_NT_MAX_TUPLES 8
 #define G2048_NT_MAX_LEN 6
 #define G2048_NT_FRAC_BITS 12 /* S = 4096: values are points x S */
+#define G2048_NT_MAX_TRACE 4        /* the longest eligibility trace of the lambda step */
+#define G2048_NT_MAX_LAMBDA_SHIFT 7 /* lambda = 2^-lambda_shift, lambda_shift in 1..7 */
 
 typedef struct g2048_ntuple_net { /* host struct, read during the call */
     int32_t num_tuples;           /* T in 1..8 */
@@ -150,6 +188,22 @@ int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t 
                     int8_t *after, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
                     int32_t lr_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
                     size_t workspace_bytes);
+
+/* `steps` lambda steps (the lambda step, above) of n envs on one net.  tc == NULL: rule TD, two launches
+   per step (evaluate; add, move the history on and step the envs).  A non-null tc: rule TC on the
+   accumulators tc, whose layout and meaning are g2048_ntuple_tc's, three launches per step (evaluate;
+   add to W; add to E and A, move the history on and step the envs).  hist int8 [trace_len][n][16]
+   (16-B aligned) and hist_len uint8 [n] are carried like after / pending; with trace_len == 0 both may
+   be null and the call is g2048_ntuple_td / _tc bit for bit.  Everything else -- the carried state,
+   stats, the workspace (of g2048_ntuple_lambda_workspace_bytes(n) bytes), the refusals -- is
+   g2048_ntuple_td's; in addition G2048_EINVAL for trace_len outside 0..G2048_NT_MAX_TRACE, lambda_shift
+   outside 1..G2048_NT_MAX_LAMBDA_SHIFT, a misaligned tc and, with trace_len > 0, a null or misaligned
+   hist or a null hist_len. */
+size_t g2048_ntuple_lambda_workspace_bytes(int64_t n);
+int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards,
+                        int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
+                        int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
+                        const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
 
 /* Expectimax search of depth 1..3 with V at the leaves (the search, above) on n boards: q int64 [n][4]
    (16-B aligned, required), leaves int64 [n][4] (nullable, 16-B aligned), legal / best uint8 [n]
