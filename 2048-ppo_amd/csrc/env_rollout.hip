@@ -8,6 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <type_traits>
+
 #include "board.hpp"
 #include "rowtable.hpp"
 #include "line11_lds.hpp"
@@ -88,11 +91,17 @@ __device__ __forceinline__ uint32_t fresh_stats(uint32_t p1, uint32_t v1, uint32
 // lines' maximum: a step's only table reads are the records of the board it produces.  A board
 // holding an exponent > 10 takes the SWAR compute path.  Workgroups are persistent over boards, so
 // large N keeps several waves per SIMD with one LDS table per CU.
-// kAddr = how a step forms its line addresses (rollout_step.hpp): the host takes the MFMA form where a
-// SIMD holds one wave (up to 256 threads per workgroup, the benchmark's 65 536 boards among them: the
-// kernel is issue-bound there and the form is 5 % faster) and the VALU form above that (at four waves per
-// SIMD the MFMA form measured 3.5 % slower at 2^20 boards and 9 % slower at 2^22: profiles/r15a).
-template <int kAddr>
+// kAddr = how a step forms its line addresses (rollout_step.hpp): the host takes the MFMA form where the
+// grid covers every board (up to 262 144 boards, one trip through the board loop; the benchmark's 65 536
+// boards, one wave per SIMD, among them: the kernel is issue-bound there and the form is 5 % faster) and
+// the VALU form above that.  With the wide stores the MFMA form lost at four waves per SIMD (profiles/r15a:
+// its per-pair scratch reload and the wait behind it); with the narrow stores, which leave no scratch, it
+// is 4 % faster than the VALU form at 98 304 .. 524 288 boards in every round and within the noise of the
+// measurement at 2^20 and 2^21 (profiles/r16a/ab_large_n*.log), so the several-trips sizes keep the VALU form.
+// kWide = how a step addresses its record (rollout_step.hpp TrajRows / TrajRowsNarrow): the narrow form,
+// uniform array bases and 32-bit lane offsets, wherever 16 n steps <= 2^32 (the benchmark's 2^26 env-steps
+// per launch among them), the wide form's 64-bit lane pointers above that (rollout_form below).
+template <int kAddr, bool kWide>
 __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ boards, int64_t n, int64_t steps,
                                                            uint4 *__restrict__ tb, uint8_t *__restrict__ ta,
                                                            int32_t *__restrict__ tp, uint32_t *__restrict__ tpot,
@@ -133,13 +142,15 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         s.ph = philox_start(rng.seed, pair + 1u, env, 1u);
         fresh_prep(s, s_row);
         refill_lines<kAddr>(s, s_row, s.S >> 24, fa);
-        // per-lane record addresses, advanced one row (n elements) per step: no array base in an SGPR
-        // pair across the loop (the loop's SGPR spills)
-        TrajRows tr{tb + li, ta + li, tp + li, tpot + li, tf + li};
+        // the record addresses of this board, from its own index in every trip of the board loop: wide,
+        // per-lane pointers advanced one row (n elements) per step and no array base in an SGPR pair across
+        // the loop; narrow, the five bases in SGPR pairs and three lane offsets advanced per step
+        using Rows = std::conditional_t<kWide, TrajRows, TrajRowsNarrow>;
+        Rows tr = Rows::at(tb, ta, tp, tpot, tf, li);
         uint64_t left = (uint64_t)steps;  // steps still to run
         if ((ctr0 & 1u) && left > 0u) {  // the launch starts on the second step of a pair
             philox_rounds<0, 5>(s.ph);
-            rollout_step<true, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+            rollout_step<true, false, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             tr.next(n);
             pair++;
             left--;
@@ -154,17 +165,17 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
             // and without masking its addresses.  The other pair keeps the carried records valid in
             // every lane whose board is <= 2^10, so a wave changes between the two freely.
             if (__all(s.S < ((kFastPairMax + 1u) << 24))) {
-                rollout_step<false, true, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+                rollout_step<false, true, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
                 tr.next(n);
-                rollout_step<true, true, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+                rollout_step<true, true, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             } else {
-                rollout_step<false, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+                rollout_step<false, false, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
                 tr.next(n);
-                rollout_step<true, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+                rollout_step<true, false, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
             }
             tr.next(n);
         }
-        if (left & 1u) rollout_step<false, false, true, kAddr>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
+        if (left & 1u) rollout_step<false, false, true, kAddr, Rows>(s, s_row, tr, rng.seed, pair + 2u, env, fa);
         boards[i] = s.b;
     }
     if (ticket) {
@@ -208,17 +219,43 @@ int g2048_env_rollout_random_adv(g2048_stream_t stream, int8_t *boards, int64_t 
                           ticket);
 }
 
+// The kernel a launch of n boards x steps takes, as G2048_ROLLOUT_FORM_* bits (include/g2048.h); a refused
+// shape gives G2048_EINVAL.
+//  - n < 2^28: a lane's byte offset into a trajectory row (16 * board id) fits 32 bits.
+//  - MFMA line addresses where the grid covers every board, i.e. up to 256 workgroups x 1024 threads (the
+//    kernel's comment): that kernel never makes a second trip through its board loop.
+//  - narrow record addressing while a lane's byte offset into the whole boards record fits 32 bits:
+//    16 n steps <= 2^32, compared as steps <= floor(2^28 / n) (n * steps may not fit 64 bits).
+static int rollout_form(int64_t n, int64_t steps) {
+    if (n < 0 || n >= (int64_t(1) << 28) || steps < 0) return G2048_EINVAL;
+    int form = 0;
+    const PersistentShape sh = persistent_shape(n);
+    if ((int64_t)sh.grid * sh.threads >= n) form |= G2048_ROLLOUT_FORM_MFMA;
+    if (n > 0 && steps > (int64_t(1) << 28) / n) form |= G2048_ROLLOUT_FORM_WIDE;
+    return form;
+}
+
+int g2048_env_rollout_form(int64_t n, int64_t steps) { return rollout_form(n, steps); }
+
+// g2048_env_rollout_force_wide: read by every launch after it is set
+static std::atomic<int> g_force_wide{0};
+
+int g2048_env_rollout_force_wide(int on) { return g_force_wide.exchange(on != 0); }
+
 static int rollout_launch(g2048_stream_t stream, int8_t *boards, int64_t n, int64_t steps, int8_t *traj_boards,
                           uint8_t *traj_actions, int32_t *traj_points, int8_t *traj_pot, uint8_t *traj_flags,
                           const g2048_rng *rng, uint32_t *ticket) {
-    // n < 2^28: a lane's byte offset into a trajectory row (16 * board id) fits the 32-bit saddr offset
-    if (n < 0 || n >= (int64_t(1) << 28) || steps < 0 || !philox_mode(rng)) return G2048_EINVAL;
+    int form = rollout_form(n, steps);
+    if (form < 0 || !philox_mode(rng)) return G2048_EINVAL;
     if (n == 0 || steps == 0) return G2048_OK;
     if (!boards || !traj_boards || !traj_actions || !traj_points || !traj_pot || !traj_flags || !aligned16(boards) ||
         !aligned16(traj_boards) || ((uintptr_t)traj_pot & 3u) || ((uintptr_t)traj_points & 3u))
         return G2048_EINVAL;
+    if (g_force_wide.load(std::memory_order_relaxed)) form |= G2048_ROLLOUT_FORM_WIDE;
     const PersistentShape sh = persistent_shape(n);
-    const auto kernel = sh.threads <= 256u ? env_rollout_kernel<kAddrMfma> : env_rollout_kernel<kAddrValu>;
+    const bool mfma = form & G2048_ROLLOUT_FORM_MFMA, wide = form & G2048_ROLLOUT_FORM_WIDE;
+    const auto kernel = mfma ? (wide ? env_rollout_kernel<kAddrMfma, true> : env_rollout_kernel<kAddrMfma, false>)
+                             : (wide ? env_rollout_kernel<kAddrValu, true> : env_rollout_kernel<kAddrValu, false>);
     hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(sh.threads), 0, (hipStream_t)stream,
                        (uint4 *)boards, n, steps, (uint4 *)traj_boards, traj_actions, traj_points, (uint32_t *)traj_pot,
                        traj_flags, rng_args(rng), ticket);

@@ -120,8 +120,9 @@ __device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__r
 // How a step (and refill_lines) turns a board into the eight line addresses: line11_addrs (packed-u16
 // VALU, about 28 instructions) or line11_addrs_mfma (one int8 MFMA against the wave's A fragment `fa`,
 // which the kernel loads at its start with every lane active, and 8 multiply-adds).  The MFMA form is
-// env_rollout_kernel's where a SIMD holds one wave (5 % faster there, slower at four waves per SIMD);
-// mc_search_kernel keeps the VALU form, the default.
+// env_rollout_kernel's where its grid covers every board (5 % faster at one wave per SIMD, 4 % at two to
+// four with the narrow record stores; env_rollout.hip's host picks); mc_search_kernel keeps the VALU form,
+// the default (rounds 15 and 16).
 constexpr int kAddrValu = 0, kAddrMfma = 1;
 
 // the records of the current board's lines from the board itself (launch start; the steps keep them
@@ -144,18 +145,67 @@ __device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__r
 // and 14..15, expcnt in 4..6, both left at their maximum, i.e. not waited for; lgkmcnt in 8..11)
 constexpr int kWaitLds = 0xC07F;
 
-struct TrajRows {  // this lane's element of row t of each time-major trajectory array (advanced by n per step)
+// Where a step's record goes: this lane's element of row t of each time-major trajectory array, advanced
+// by one row (n elements) per step.  Two forms (env_rollout.hip's host picks):
+//  - TrajRows, the wide form: five per-lane 64-bit pointers, valid at every shape.
+//  - TrajRowsNarrow: the five array bases, wave-uniform and constant (SGPR pairs), and three per-lane
+//    32-bit BYTE offsets -- o1 into actions and flags, o4 into points and potentials, o16 into boards --
+//    that start at i, 4 i, 16 i and advance by n, 4 n, 16 n.  A store is `base + zext(offset)`, the
+//    scalar-base form of global_store (no 64-bit vector add), so the largest offset formed for a store,
+//    16 (n steps - 1), has to fit 32 bits: valid while 16 n steps <= 2^32.  (The advance behind the last
+//    step may wrap; nothing is stored through it.)
+struct TrajRows {
     uint4 *b;
     uint8_t *a;
     int32_t *p;
     uint32_t *pot;
     uint8_t *f;
+    // board i's row 0
+    __device__ __forceinline__ static TrajRows at(uint4 *tb, uint8_t *ta, int32_t *tp, uint32_t *tpot, uint8_t *tf, uint32_t i) {
+        return TrajRows{tb + i, ta + i, tp + i, tpot + i, tf + i};
+    }
     __device__ __forceinline__ void next(int64_t n) {
         b += n;
         a += n;
         p += n;
         pot += n;
         f += n;
+    }
+    __device__ __forceinline__ void put_b(const uint4 &v) const { *b = v; }
+    __device__ __forceinline__ void put_a(uint32_t v) const { *a = (uint8_t)v; }
+    __device__ __forceinline__ void put_p(uint32_t v) const { *p = (int32_t)v; }
+    __device__ __forceinline__ void put_pot(uint32_t v) const { *pot = v; }
+    __device__ __forceinline__ void put_f(uint32_t v) { *f = (uint8_t)v; }
+};
+struct TrajRowsNarrow {
+    char *b, *a, *p, *pot, *f;
+    uint32_t o1, o4, o16;
+    // board i's row 0 (i < 2^28)
+    __device__ __forceinline__ static TrajRowsNarrow at(uint4 *tb, uint8_t *ta, int32_t *tp, uint32_t *tpot, uint8_t *tf, uint32_t i) {
+        return TrajRowsNarrow{(char *)tb, (char *)ta, (char *)tp, (char *)tpot, (char *)tf, i, 4u * i, 16u * i};
+    }
+    // One add per offset and step.  The empty asm makes each sum a value of its own: without it the
+    // compiler keeps the even step's offsets across the pair and forms the odd step's beside them,
+    // three more adds per pair.
+    __device__ __forceinline__ void next(int64_t n) {
+        const uint32_t n1 = (uint32_t)n;
+        o1 += n1;
+        o4 += 4u * n1;
+        o16 += 16u * n1;
+        asm("" : "+v"(o1), "+v"(o4), "+v"(o16));
+    }
+    __device__ __forceinline__ void put_b(const uint4 &v) const { *reinterpret_cast<uint4 *>(b + o16) = v; }
+    __device__ __forceinline__ void put_a(uint32_t v) const { *reinterpret_cast<uint8_t *>(a + o1) = (uint8_t)v; }
+    __device__ __forceinline__ void put_p(uint32_t v) const { *reinterpret_cast<int32_t *>(p + o4) = (int32_t)v; }
+    __device__ __forceinline__ void put_pot(uint32_t v) const { *reinterpret_cast<uint32_t *>(pot + o4) = v; }
+    // The flags store stands behind the masked reset block, in a basic block of its own, and instruction
+    // selection works block by block: it would see the zero-extended offset as a 64-bit value from another
+    // block and add it to the base with a v_lshl_add_u64 (and keep a zero register for the high half).
+    // The empty asm redefines o1 in the store's block, in place (no copy: every later use reads the
+    // redefined value), so the extension is selected with the store, into its scalar-base form.
+    __device__ __forceinline__ void put_f(uint32_t v) {
+        asm("" : "+v"(o1));
+        *reinterpret_cast<uint8_t *>(f + o1) = (uint8_t)v;
     }
 };
 
@@ -164,8 +214,8 @@ struct TrajRows {  // this lane's element of row t of each time-major trajectory
 // step (no SWAR fallback, no address masking).  One 32-bit word u per step: action
 // k = floor(u * nlegal / 2^32); the low word r of that product (uniform given k) picks the spawn cell
 // and value.  kTraj = false never touches tr.
-template <bool kOdd, bool kSmall, bool kTraj, int kAddr = kAddrValu>
-__device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__restrict__ tab, const TrajRows &tr,
+template <bool kOdd, bool kSmall, bool kTraj, int kAddr = kAddrValu, class Rows = TrajRows>
+__device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__restrict__ tab, Rows &tr,
                                              uint64_t seed, uint64_t next_pair, uint32_t env, const i32x4 &fa = i32x4{}) {
     // kTraj: explicit waits for every LDS load in flight (a reset's reload, fresh_prep's two reads), so
     // that the wait-count pass sees an empty queue behind them.  Where the fast pair joins the path
@@ -178,7 +228,7 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     // fast pair's odd step.  They pay only together: the first alone, the first two, and the last two
     // were each slower than none, all three are 1.1-1.6 % faster.
     if constexpr (kTraj && (!kOdd || kSmall)) __builtin_amdgcn_s_waitcnt(kWaitLds);
-    if constexpr (kTraj) *tr.b = s.b;
+    if constexpr (kTraj) tr.put_b(s.b);
     const uint32_t u = kOdd ? s.D.y : s.D.x;
     const uint64_t pa = (uint64_t)u * (uint32_t)__popc(s.legal);
     const uint32_t a = kth_bit4(s.legal, (uint32_t)(pa >> 32)), r = (uint32_t)pa;
@@ -324,8 +374,8 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
         asm volatile("" : "+v"(s.ph.c0), "+v"(s.ph.c1), "+v"(s.ph.c2), "+v"(s.ph.c3), "+v"(R0.y), "+v"(R1.y), "+v"(R2.y), "+v"(R3.y),
                           "+v"(C0.y), "+v"(C1.y), "+v"(C2.y), "+v"(C3.y));
     if constexpr (kTraj) {
-        *tr.a = (uint8_t)a;
-        *tr.p = (int32_t)pts;
+        tr.put_a(a);
+        tr.put_p(pts);
     }
     // line sums of the next board (bits 16..31 of a sum hold the points / maximum fields' sum, which no
     // byte select below reads) and of the pre-spawn board
@@ -351,7 +401,7 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
             S = carry_pack(mono_add_tile(ms, pre, sp, v));
         }
         const uint32_t mono_a = mono_value_packed(sa);
-        *tr.pot = mono_b | (mono_a << 8) | ((uint32_t)s.empt_b << 16) | (empt_a << 24);
+        tr.put_pot(mono_b | (mono_a << 8) | ((uint32_t)s.empt_b << 16) | (empt_a << 24));
         uint32_t fl = s.legal;
         s.S = S;
         s.empt_b = (int)empt_a - 1;
@@ -377,7 +427,7 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
             fl = FLAG_DONE | FLAG_RESET | s.legal;
             s.empt_b = 14;
         }
-        *tr.f = (uint8_t)fl;
+        tr.put_f(fl);
     } else {  // the finished game stays (legal == 0 ends the playout); only the table guard is carried
         s.M = max(Ma, v);
         s.score += pts;

@@ -237,6 +237,18 @@ def env_rollout_random(boards, steps, traj_boards, traj_actions, traj_points, tr
         _call("g2048_env_rollout_random_adv", *args, _dev(ticket, torch.int32, "ticket"))
 
 
+def env_rollout_form(n: int, steps: int) -> int:
+    """The kernel env_rollout_random launches for n boards x steps: ROLLOUT_FORM_MFMA | ROLLOUT_FORM_WIDE
+    bits, or EINVAL for a shape it refuses (g2048_env_rollout_form: host only, no device)."""
+    return int(load().g2048_env_rollout_form(int(n), int(steps)))
+
+
+def env_rollout_force_wide(on: bool) -> bool:
+    """Test only: every later env_rollout_random launch takes the wide record addressing (True) or the
+    form of its shape again (False).  Returns the previous setting."""
+    return bool(load().g2048_env_rollout_force_wide(int(bool(on))))
+
+
 def mc_search_workspace_bytes(n: int, playouts: int) -> int:
     return int(load().g2048_mc_search_workspace_bytes(int(n), int(playouts)))
 

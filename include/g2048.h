@@ -119,6 +119,26 @@ int g2048_env_rollout_random_adv(g2048_stream_t stream, int8_t *boards, int64_t 
                                  uint8_t *traj_actions, int32_t *traj_points, int8_t *traj_pot, uint8_t *traj_flags,
                                  const g2048_rng *rng, uint32_t *ticket);
 
+/* The kernel that g2048_env_rollout_random / _adv launch for n boards x steps, as a sum of the two bits
+   below, or G2048_EINVAL for a shape they refuse (n < 0, n >= 2^28, steps < 0).  A pure function of the
+   shape: no device, no state, g2048_env_rollout_force_wide does not change it.
+     MFMA   a step's eight LDS line addresses come from one int8 MFMA (up to 262 144 boards: the grid of
+            256 workgroups of up to 1024 threads covers every board); otherwise from packed-u16 VALU
+            arithmetic.
+     WIDE   a step's record stores go through per-lane 64-bit pointers; otherwise (narrow) through the five
+            array bases and per-lane 32-bit byte offsets, which holds while 16 n steps <= 2^32, i.e.
+            n steps <= 2^28.
+   The records are bit for bit the same in all four. */
+#define G2048_ROLLOUT_FORM_MFMA 1
+#define G2048_ROLLOUT_FORM_WIDE 2
+int g2048_env_rollout_form(int64_t n, int64_t steps);
+
+/* TEST ONLY.  on != 0: every later g2048_env_rollout_random / _adv launch of this process takes the wide
+   record addressing whatever its shape (so that the form the large shapes take runs at test sizes);
+   0 puts the choice back to g2048_env_rollout_form's.  Returns the previous setting (0 / 1).  Process-wide
+   and not synchronised with launches in flight on other threads. */
+int g2048_env_rollout_force_wide(int on);
+
 /* Pure Monte-Carlo playout search on n root boards (no reference counterpart: the search baseline a
    trained agent's `evaluate` score is compared with).  For every board i and action a, `playouts`
    (P, 1..4096) random games of at most `depth` (D, 0..65 536) moves are played after the move a, one

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Per-basic-block instruction counts of env_rollout_kernel from its assembly (make asm):
-python3 tools/asm_blocks.py /tmp/env_rollout.s [min_valu]
-(the first env_rollout_kernel instantiation of the file: kAddrMfma's; blocks(path, "env_rollout_kernelILi0E")
-reads the VALU-address one)
+python3 tools/asm_blocks.py /tmp/env_rollout.s [min_valu] [--kernel NAME]
+(the first env_rollout_kernel instantiation of the file unless --kernel names another by a piece of its
+mangled name: env_rollout_kernelILi1ELb0E is <kAddrMfma, narrow>, the benchmark's; ILi1ELb1E <kAddrMfma, wide>;
+ILi0ELb0E / ILi0ELb1E the VALU-address pair)
 
 One line per block: label, VALU, of which v_cndmask, LDS reads, scratch_* instructions,
 v_readlane / v_writelane, s_waitcnt lgkmcnt, and the branch targets, so the inner loop's header, its two
@@ -59,12 +60,17 @@ def path_totals(path, labels, kernel="env_rollout_kernel"):
 
 
 def main():
+    kernel = "env_rollout_kernel"
+    if "--kernel" in sys.argv:
+        k = sys.argv.index("--kernel")
+        kernel = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
     if len(sys.argv) > 3 and sys.argv[2] == "path":
-        return path_totals(sys.argv[1], sys.argv[3])
+        return path_totals(sys.argv[1], sys.argv[3], kernel)
     path = sys.argv[1]
     min_valu = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     print(f"{'block':<12}{'ins':>6}{'valu':>6}{'cnd':>5}{'lds_rd':>7}{'scr':>5}{'lane':>5}{'lgkm':>5}  branches")
-    for b in blocks(path):
+    for b in blocks(path, kernel):
         ins = b["ins"]
         op = [i.split()[0] for i in ins]
         valu = sum(o.startswith("v_") and not o.startswith(("v_readlane", "v_writelane", "v_readfirstlane")) for o in op)
