@@ -17,6 +17,10 @@
 // nt_tc_update_kernel adds to the records (64-bit atomics) and ends like nt_td_update_kernel.
 // The lambda step (g2048_ntuple_lambda, lambda = 2^-s) has the same launches with writing kernels of its
 // own (nt_lambda_*): they also add D >> k s to the after-state k moves older, kept per env in hist.
+// A net with stages (stage_map != 0) has G sets of tables, [G][T][16^K]: every board evaluated or updated
+// goes to the tuple rows of its own stage (nt_row of ntuple_net.hpp, a function of its largest nibble), in
+// kernels instantiated with S = true beside the one-stage ones.  nt_stage_kernel writes the stages of
+// boards, nt_promote_kernel adds one stage's tables to another's (g2048_ntuple_promote).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,10 +37,11 @@ namespace {
 constexpr int64_t kMaxD = int64_t(1) << 30;
 
 // D added to each of the 8 T weights V(b) reads, with multiplicity; the weights wrap
-template <int K>
+template <int K, bool S>
 __device__ __forceinline__ void nt_add(const NtArgs &net, uint64_t x, int32_t D) {
+    const uint32_t row = nt_row<S>(net, x);
     for (int t = 0; t < net.T; t++) {
-        uint32_t *W = (uint32_t *)net.w + ((size_t)t << (4 * K));
+        uint32_t *W = (uint32_t *)net.w + ((size_t)(row + t) << (4 * K));
 #pragma unroll
         for (int g = 0; g < 8; g++)
             __hip_atomic_fetch_add(W + nt_index<K>(x, net.cells[8 * t + g]), (uint32_t)D, __ATOMIC_RELAXED,
@@ -49,7 +54,7 @@ struct NtChoice {
     uint32_t legal, best;
 };
 
-template <int K>
+template <int K, bool S>
 __device__ __forceinline__ NtChoice nt_choose(const NtArgs &net, const uint4 &b) {
     NtChoice c;
     c.legal = 0u;
@@ -61,7 +66,7 @@ __device__ __forceinline__ NtChoice nt_choose(const NtArgs &net, const uint4 &b)
         const uint4 s = apply_move(b, a, pts, mx);
         c.q[a] = INT64_MIN;
         if (!eq4(s, b)) {
-            c.q[a] = ((long long)pts << kFrac) + nt_value<K>(net, nt_pack(s));
+            c.q[a] = ((long long)pts << kFrac) + nt_value<K, S>(net, nt_pack(s));
             c.legal |= 1u << a;
             if (c.best == 0xFFu || c.q[a] > bq) {
                 bq = c.q[a];
@@ -72,21 +77,21 @@ __device__ __forceinline__ NtChoice nt_choose(const NtArgs &net, const uint4 &b)
     return c;
 }
 
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_value_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                        long long *__restrict__ value, uint32_t n) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    value[i] = nt_value<K>(net, nt_pack(boards[i]));
+    value[i] = nt_value<K, S>(net, nt_pack(boards[i]));
 }
 
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_choose_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                         long long *__restrict__ q, uint8_t *__restrict__ legal,
                                                         uint8_t *__restrict__ best, uint32_t n) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const NtChoice c = nt_choose<K>(net, boards[i]);
+    const NtChoice c = nt_choose<K, S>(net, boards[i]);
     if (q) {
         reinterpret_cast<longlong2 *>(q)[2u * i] = make_longlong2(c.q[0], c.q[1]);
         reinterpret_cast<longlong2 *>(q)[2u * i + 1u] = make_longlong2(c.q[2], c.q[3]);
@@ -95,8 +100,32 @@ __global__ __launch_bounds__(256) void nt_choose_kernel(NtArgs net, const uint4 
     if (best) best[i] = (uint8_t)c.best;
 }
 
+// stage[i] = stage(boards[i]); a one-stage net (map 0) gives 0
+__global__ __launch_bounds__(256) void nt_stage_kernel(uint64_t stage_map, const uint4 *__restrict__ boards,
+                                                       uint8_t *__restrict__ stage, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    stage[i] = (uint8_t)nt_stage(stage_map, nt_pack(boards[i]));
+}
+
+// Promotion: to[j] += from[j] (int32, wrapping) over the `quads` 16-byte words of one stage's tables, a
+// grid-stride loop of 16-byte loads and stores; the two stages are different, so the ranges are disjoint
+constexpr unsigned kPromoteBlocks = 2048;  // 8 workgroups of 256 lanes per compute unit
+__global__ __launch_bounds__(256) void nt_promote_kernel(const uint4 *__restrict__ from, uint4 *__restrict__ to,
+                                                         uint32_t quads) {
+    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < quads; j += gridDim.x * 256u) {
+        const uint4 f = from[j];
+        uint4 t = to[j];
+        t.x += f.x;
+        t.y += f.y;
+        t.z += f.z;
+        t.w += f.w;
+        to[j] = t;
+    }
+}
+
 // TD step, the reading half: the greedy action of the board and the D of the pending after-state
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_td_eval_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                          const uint4 *__restrict__ after,
                                                          const uint8_t *__restrict__ pending, int lr_shift,
@@ -104,14 +133,14 @@ __global__ __launch_bounds__(256) void nt_td_eval_kernel(NtArgs net, const uint4
                                                          uint32_t n) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const NtChoice c = nt_choose<K>(net, boards[i]);
+    const NtChoice c = nt_choose<K, S>(net, boards[i]);
     long long target = 0;
 #pragma unroll
     for (uint32_t a = 0u; a < 4u; a++) target = c.best == a ? c.q[a] : target;
     const uint32_t p = pending[i];
     long long D = 0;
     if (p != 0u) {
-        const long long delta = (p == 2u ? 0 : target) - nt_value<K>(net, nt_pack(after[i]));
+        const long long delta = (p == 2u ? 0 : target) - nt_value<K, S>(net, nt_pack(after[i]));
         D = (delta + (1ll << (lr_shift - 1))) >> lr_shift;
         D = D < -kMaxD ? -kMaxD : D > kMaxD ? kMaxD : D;
     }
@@ -159,7 +188,7 @@ __device__ __forceinline__ void nt_count_updates(long long *stats, bool updated)
 }
 
 // TD step, the writing half: the update of the pending after-state, then the env step
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_td_update_kernel(NtArgs net, uint4 *__restrict__ boards,
                                                            uint4 *__restrict__ after, uint8_t *__restrict__ pending,
                                                            long long *__restrict__ run_score,
@@ -173,7 +202,7 @@ __global__ __launch_bounds__(256) void nt_td_update_kernel(NtArgs net, uint4 *__
         const uint32_t p = pending[i];
         const int32_t D = ws_d[i];
         updated = p != 0u;
-        if (updated && D != 0) nt_add<K>(net, nt_pack(after[i]), D);
+        if (updated && D != 0) nt_add<K, S>(net, nt_pack(after[i]), D);
         nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
     }
     nt_count_updates(stats, updated);
@@ -197,7 +226,7 @@ __device__ __forceinline__ int32_t nt_tc_share(long long E, unsigned long long A
 // next launch, so every lane sees the records before the step's adds.
 typedef long long NtRecord __attribute__((ext_vector_type(2)));  // (E, A): one 16-byte load, not two of 8
 
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const NtRecord *__restrict__ tc,
                                                             const uint4 *__restrict__ after,
                                                             const uint8_t *__restrict__ pending,
@@ -207,8 +236,9 @@ __global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const Nt
     const int32_t D = ws_d[i];
     if (pending[i] == 0u || D == 0) return;
     const uint64_t x = nt_pack(after[i]);
+    const uint32_t row = nt_row<S>(net, x);
     for (int t = 0; t < net.T; t++) {
-        const size_t base = (size_t)t << (4 * K);
+        const size_t base = (size_t)(row + t) << (4 * K);
         uint32_t idx[8];
         NtRecord r[8];
 #pragma unroll
@@ -225,7 +255,7 @@ __global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const Nt
 }
 
 // TC step, the last launch: D to E and |D| to A of the same 8 T records, then the env step
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_tc_update_kernel(NtArgs net, unsigned long long *__restrict__ tc,
                                                            uint4 *__restrict__ boards, uint4 *__restrict__ after,
                                                            uint8_t *__restrict__ pending,
@@ -243,8 +273,9 @@ __global__ __launch_bounds__(256) void nt_tc_update_kernel(NtArgs net, unsigned 
         if (updated && D != 0) {
             const uint64_t x = nt_pack(after[i]);
             const unsigned long long dE = (unsigned long long)(long long)D, dA = D < 0 ? 0ull - dE : dE;
+            const uint32_t row = nt_row<S>(net, x);
             for (int tt = 0; tt < net.T; tt++) {
-                unsigned long long *rec = tc + ((size_t)tt << (4 * K + 1));
+                unsigned long long *rec = tc + ((size_t)(row + tt) << (4 * K + 1));
 #pragma unroll
                 for (int g = 0; g < 8; g++) {
                     const size_t k = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
@@ -311,7 +342,7 @@ __device__ __forceinline__ void nt_trace_store(const NtTrace &tr, uint4 *hist, u
 }
 
 // TD(lambda), the writing half: D_k to the 8 T weights of s_k, then the history and the env step
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_lambda_td_update_kernel(
     NtArgs net, uint4 *__restrict__ boards, uint4 *__restrict__ after, uint4 *__restrict__ hist,
     uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending, long long *__restrict__ run_score,
@@ -329,7 +360,7 @@ __global__ __launch_bounds__(256) void nt_lambda_td_update_kernel(
 #pragma unroll
             for (int k = 0; k <= kMaxTrace; k++) {
                 const int32_t Dk = nt_decay(D, k * s);
-                if ((uint32_t)k <= tr.len && Dk != 0) nt_add<K>(net, tr.x[k], Dk);
+                if ((uint32_t)k <= tr.len && Dk != 0) nt_add<K, S>(net, tr.x[k], Dk);
             }
         }
         nt_trace_store(tr, hist, hist_len, h, p, ws_act[i] != 0xFFu, n, i);
@@ -340,7 +371,7 @@ __global__ __launch_bounds__(256) void nt_lambda_td_update_kernel(
 
 // TC(lambda), the launch between: per (k, tuple) the 8 records of s_k are gathered together and each
 // weight takes its share of D_k.  hist is only read here.
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_lambda_tc_weights_kernel(
     NtArgs net, const NtRecord *__restrict__ tc, const uint4 *__restrict__ after, const uint4 *__restrict__ hist,
     const uint8_t *__restrict__ hist_len, const uint8_t *__restrict__ pending, const int32_t *__restrict__ ws_d, int h,
@@ -355,8 +386,9 @@ __global__ __launch_bounds__(256) void nt_lambda_tc_weights_kernel(
         const int32_t Dk = nt_decay(D, k * s);
         if ((uint32_t)k > tr.len || Dk == 0) continue;
         const uint64_t x = tr.x[k];
+        const uint32_t row = nt_row<S>(net, x);
         for (int t = 0; t < net.T; t++) {
-            const size_t base = (size_t)t << (4 * K);
+            const size_t base = (size_t)(row + t) << (4 * K);
             uint32_t idx[8];
             NtRecord r[8];
 #pragma unroll
@@ -374,7 +406,7 @@ __global__ __launch_bounds__(256) void nt_lambda_tc_weights_kernel(
 }
 
 // TC(lambda), the last launch: D_k to E and |D_k| to A of the records of s_k, then as the TD(lambda) one
-template <int K>
+template <int K, bool S>
 __global__ __launch_bounds__(256) void nt_lambda_tc_update_kernel(
     NtArgs net, unsigned long long *__restrict__ tc, uint4 *__restrict__ boards, uint4 *__restrict__ after,
     uint4 *__restrict__ hist, uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending,
@@ -395,8 +427,9 @@ __global__ __launch_bounds__(256) void nt_lambda_tc_update_kernel(
                 if ((uint32_t)k > tr.len || Dk == 0) continue;
                 const uint64_t x = tr.x[k];
                 const unsigned long long dE = (unsigned long long)(long long)Dk, dA = Dk < 0 ? 0ull - dE : dE;
+                const uint32_t row = nt_row<S>(net, x);
                 for (int tt = 0; tt < net.T; tt++) {
-                    unsigned long long *rec = tc + ((size_t)tt << (4 * K + 1));
+                    unsigned long long *rec = tc + ((size_t)(row + tt) << (4 * K + 1));
 #pragma unroll
                     for (int g = 0; g < 8; g++) {
                         const size_t j = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
@@ -419,33 +452,66 @@ size_t td_workspace_bytes(int64_t n) { return align16((size_t)n * 4) + align16((
 
 extern "C" {
 
+// nt_call_<call>(stream, net, stage_map, ...): the body of g2048_ntuple_<call> (stage_map 0) and of its twin
+// g2048_ntuple_staged_<call>, both at the end of the file
+
 size_t g2048_ntuple_weight_count(const g2048_ntuple_net *net) {
     NtArgs a;
-    if (!make_args(net, a)) return 0;
+    if (!make_args(net, 0, a)) return 0;
     return (size_t)net->num_tuples << (4 * net->tuple_len);
 }
 
-int g2048_ntuple_value(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *value,
+size_t g2048_ntuple_staged_weight_count(const g2048_ntuple_staged_net *snet) {
+    NtArgs a;
+    if (!snet || !make_args(&snet->net, snet->stage_map, a)) return 0;
+    return ((size_t)a.G * snet->net.num_tuples) << (4 * snet->net.tuple_len);
+}
+
+int g2048_ntuple_stage(g2048_stream_t stream, const g2048_ntuple_staged_net *snet, const int8_t *boards,
+                       uint8_t *stage, int64_t n) {
+    NtArgs a;
+    if (!snet || !make_args(&snet->net, snet->stage_map, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
+    if (n == 0) return G2048_OK;
+    if (!boards || !aligned16(boards) || !stage) return G2048_EINVAL;
+    hipLaunchKernelGGL(nt_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       a.stage_map, (const uint4 *)boards, stage, (uint32_t)n);
+    return launch_status();
+}
+
+int g2048_ntuple_promote(g2048_stream_t stream, const g2048_ntuple_staged_net *snet, int32_t from, int32_t to) {
+    NtArgs a;
+    if (!snet || !make_args(&snet->net, snet->stage_map, a)) return G2048_EINVAL;
+    if (from < 0 || from >= a.G || to < 0 || to >= a.G || from == to) return G2048_EINVAL;
+    const size_t quads = ((size_t)snet->net.num_tuples << (4 * snet->net.tuple_len)) / 4;  // at most 2^25: K >= 1, a multiple of 4
+    const uint4 *w = (const uint4 *)a.w;
+    const unsigned blocks = (unsigned)((quads + 255) / 256 < kPromoteBlocks ? (quads + 255) / 256 : kPromoteBlocks);
+    hipLaunchKernelGGL(nt_promote_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w + (size_t)from * quads,
+                       (uint4 *)a.w + (size_t)to * quads, (uint32_t)quads);
+    return launch_status();
+}
+
+static int nt_call_value(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, const int8_t *boards,
+                         int64_t *value,
                        int64_t n) {
     NtArgs a;
-    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
     if (!boards || !aligned16(boards) || !value) return G2048_EINVAL;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    G2048_NT_DISPATCH(net->tuple_len, hipLaunchKernelGGL(nt_value_kernel<kK>, grid, block, 0, (hipStream_t)stream, a,
+    G2048_NT_DISPATCH(a, net->tuple_len, hipLaunchKernelGGL((nt_value_kernel<kK, kS>), grid, block, 0, (hipStream_t)stream, a,
                                                          (const uint4 *)boards, (long long *)value, (uint32_t)n));
     return launch_status();
 }
 
-int g2048_ntuple_choose(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *q,
+static int nt_call_choose(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, const int8_t *boards, int64_t *q,
                         uint8_t *legal, uint8_t *best, int64_t n) {
     NtArgs a;
-    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
     if (!q && !legal && !best) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
     if (!boards || !aligned16(boards) || !aligned16(q)) return G2048_EINVAL;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    G2048_NT_DISPATCH(net->tuple_len, hipLaunchKernelGGL(nt_choose_kernel<kK>, grid, block, 0, (hipStream_t)stream, a,
+    G2048_NT_DISPATCH(a, net->tuple_len, hipLaunchKernelGGL((nt_choose_kernel<kK, kS>), grid, block, 0, (hipStream_t)stream, a,
                                                          (const uint4 *)boards, (long long *)q, legal, best,
                                                          (uint32_t)n));
     return launch_status();
@@ -456,11 +522,11 @@ size_t g2048_ntuple_td_workspace_bytes(int64_t n) {
     return td_workspace_bytes(n < 1 ? 1 : n);
 }
 
-int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
+static int nt_call_td(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int8_t *boards, int8_t *after,
                     uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                     const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes_in) {
     NtArgs a;
-    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
     if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
@@ -474,14 +540,14 @@ int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *
     const RngArgs r = rng_args(rng);
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_td_eval_kernel<kK>, grid, block, 0, st, a, (const uint4 *)boards,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
                                              (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
                                              (uint32_t)n));
         int s = launch_status();
         if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_td_update_kernel<kK>, grid, block, 0, st, a, (uint4 *)boards,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_td_update_kernel<kK, kS>), grid, block, 0, st, a, (uint4 *)boards,
                                              (uint4 *)after, pending, (long long *)run_score, (const int32_t *)ws_d,
                                              (const uint8_t *)ws_act, r, (uint64_t)t, (long long *)stats, (uint32_t)n));
         s = launch_status();
@@ -492,11 +558,11 @@ int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *
 
 size_t g2048_ntuple_tc_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
 
-int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+static int nt_call_tc(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc, int8_t *boards, int8_t *after,
                     uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                     const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes_in) {
     NtArgs a;
-    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
     if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
     if (!tc || !aligned16(tc)) return G2048_EINVAL;
@@ -511,20 +577,20 @@ int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t 
     const RngArgs r = rng_args(rng);
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_td_eval_kernel<kK>, grid, block, 0, st, a, (const uint4 *)boards,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
                                              (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
                                              (uint32_t)n));
         int s = launch_status();
         if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_tc_weights_kernel<kK>, grid, block, 0, st, a, (const NtRecord *)tc,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_tc_weights_kernel<kK, kS>), grid, block, 0, st, a, (const NtRecord *)tc,
                                              (const uint4 *)after, (const uint8_t *)pending, (const int32_t *)ws_d,
                                              (uint32_t)n));
         s = launch_status();
         if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_tc_update_kernel<kK>, grid, block, 0, st, a, (unsigned long long *)tc,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_tc_update_kernel<kK, kS>), grid, block, 0, st, a, (unsigned long long *)tc,
                                              (uint4 *)boards, (uint4 *)after, pending, (long long *)run_score,
                                              (const int32_t *)ws_d, (const uint8_t *)ws_act, r, (uint64_t)t,
                                              (long long *)stats, (uint32_t)n));
@@ -536,12 +602,12 @@ int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t 
 
 size_t g2048_ntuple_lambda_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
 
-int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+static int nt_call_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc, int8_t *boards, int8_t *after,
                         int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
                         int32_t lr_shift, int32_t trace_len, int32_t lambda_shift, const g2048_rng *rng, int64_t *stats,
                         void *workspace, size_t workspace_bytes_in) {
     NtArgs a;
-    if (!make_args(net, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
     if (trace_len < 0 || trace_len > G2048_NT_MAX_TRACE || lambda_shift < 1 || lambda_shift > G2048_NT_MAX_LAMBDA_SHIFT)
         return G2048_EINVAL;
@@ -560,29 +626,29 @@ int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int6
     const int h = trace_len, ls = lambda_shift;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(net->tuple_len,
-                          hipLaunchKernelGGL(nt_td_eval_kernel<kK>, grid, block, 0, st, a, (const uint4 *)boards,
+        G2048_NT_DISPATCH(a, net->tuple_len,
+                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
                                              (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
                                              (uint32_t)n));
         int s = launch_status();
         if (s != G2048_OK) return s;
         if (tc) {
-            G2048_NT_DISPATCH(net->tuple_len,
-                              hipLaunchKernelGGL(nt_lambda_tc_weights_kernel<kK>, grid, block, 0, st, a,
+            G2048_NT_DISPATCH(a, net->tuple_len,
+                              hipLaunchKernelGGL((nt_lambda_tc_weights_kernel<kK, kS>), grid, block, 0, st, a,
                                                  (const NtRecord *)tc, (const uint4 *)after, (const uint4 *)hist,
                                                  (const uint8_t *)hist_len, (const uint8_t *)pending,
                                                  (const int32_t *)ws_d, h, ls, (uint32_t)n));
             s = launch_status();
             if (s != G2048_OK) return s;
-            G2048_NT_DISPATCH(net->tuple_len,
-                              hipLaunchKernelGGL(nt_lambda_tc_update_kernel<kK>, grid, block, 0, st, a,
+            G2048_NT_DISPATCH(a, net->tuple_len,
+                              hipLaunchKernelGGL((nt_lambda_tc_update_kernel<kK, kS>), grid, block, 0, st, a,
                                                  (unsigned long long *)tc, (uint4 *)boards, (uint4 *)after, (uint4 *)hist,
                                                  hist_len, pending, (long long *)run_score, (const int32_t *)ws_d,
                                                  (const uint8_t *)ws_act, h, ls, r, (uint64_t)t, (long long *)stats,
                                                  (uint32_t)n));
         } else {
-            G2048_NT_DISPATCH(net->tuple_len,
-                              hipLaunchKernelGGL(nt_lambda_td_update_kernel<kK>, grid, block, 0, st, a, (uint4 *)boards,
+            G2048_NT_DISPATCH(a, net->tuple_len,
+                              hipLaunchKernelGGL((nt_lambda_td_update_kernel<kK, kS>), grid, block, 0, st, a, (uint4 *)boards,
                                                  (uint4 *)after, (uint4 *)hist, hist_len, pending, (long long *)run_score,
                                                  (const int32_t *)ws_d, (const uint8_t *)ws_act, h, ls, r, (uint64_t)t,
                                                  (long long *)stats, (uint32_t)n));
@@ -591,6 +657,69 @@ int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int6
         if (s != G2048_OK) return s;
     }
     return G2048_OK;
+}
+
+// ---- the entry points: a one-stage call is its twin on a staged net with the map 0
+#define NT_STAGED(net) ((net) ? &(net)->net : nullptr), ((net) ? (net)->stage_map : 0)
+
+int g2048_ntuple_value(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *value,
+                       int64_t n) {
+    return nt_call_value(stream, net, 0, boards, value, n);
+}
+int g2048_ntuple_staged_value(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                              int64_t *value, int64_t n) {
+    return nt_call_value(stream, NT_STAGED(net), boards, value, n);
+}
+
+int g2048_ntuple_choose(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t *q,
+                        uint8_t *legal, uint8_t *best, int64_t n) {
+    return nt_call_choose(stream, net, 0, boards, q, legal, best, n);
+}
+int g2048_ntuple_staged_choose(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                               int64_t *q, uint8_t *legal, uint8_t *best, int64_t n) {
+    return nt_call_choose(stream, NT_STAGED(net), boards, q, legal, best, n);
+}
+
+int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
+                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
+    return nt_call_td(stream, net, 0, boards, after, pending, run_score, n, steps, lr_shift, rng, stats, workspace,
+                      workspace_bytes);
+}
+int g2048_ntuple_staged_td(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int8_t *boards, int8_t *after,
+                           uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                           const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
+    return nt_call_td(stream, NT_STAGED(net), boards, after, pending, run_score, n, steps, lr_shift, rng, stats,
+                      workspace, workspace_bytes);
+}
+
+int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
+    return nt_call_tc(stream, net, 0, tc, boards, after, pending, run_score, n, steps, lr_shift, rng, stats, workspace,
+                      workspace_bytes);
+}
+int g2048_ntuple_staged_tc(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                           int8_t *after, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                           int32_t lr_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
+                           size_t workspace_bytes) {
+    return nt_call_tc(stream, NT_STAGED(net), tc, boards, after, pending, run_score, n, steps, lr_shift, rng, stats,
+                      workspace, workspace_bytes);
+}
+
+int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
+                        int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                        int32_t lr_shift, int32_t trace_len, int32_t lambda_shift, const g2048_rng *rng, int64_t *stats,
+                        void *workspace, size_t workspace_bytes) {
+    return nt_call_lambda(stream, net, 0, tc, boards, after, hist, hist_len, pending, run_score, n, steps, lr_shift,
+                          trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
+}
+int g2048_ntuple_staged_lambda(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                               int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
+                               int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
+                               const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
+    return nt_call_lambda(stream, NT_STAGED(net), tc, boards, after, hist, hist_len, pending, run_score, n, steps,
+                          lr_shift, trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
 }
 
 }  // extern "C"

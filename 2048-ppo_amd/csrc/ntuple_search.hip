@@ -6,8 +6,8 @@
 // legal moves only and a board without one is worth 0.  So the two lane mappings below (NARROW, WIDE)
 // give the same integers whatever the order of their reductions.
 //
-// The tree walk is expectimax.hip's compile-time recursion over the board in four dwords (nts_M<P, K> /
-// nts_A<P, K>, P <= 2 plies below a lane, K the tuple length), with no stack and no scratch.  The leaf
+// The tree walk is expectimax.hip's compile-time recursion over the board in four dwords (nts_M<P, K, S> /
+// nts_A<P, K, S>, P <= 2 plies below a lane, K the tuple length), with no stack and no scratch.  The leaf
 // is 8 T dependent-address dword gathers, so the kernels are bound by gather latency: the innermost
 // maximum, M(b, 1), issues the gathers of all its legal moves' after-states, tuple by tuple (up to 32
 // in flight per lane), before it sums any.
@@ -53,17 +53,18 @@ __device__ __forceinline__ int64_t floor_div10e(int64_t x, uint32_t E) {
 
 __device__ __forceinline__ int64_t gain_of(uint32_t pts) { return (int64_t)((uint64_t)pts << kFrac); }
 
-template <int P, int K>
+template <int P, int K, bool S>
 __device__ __forceinline__ int64_t nts_A(const uint4 &s, const NtArgs &net, uint32_t &leaves);
 
 // M(b, P), P >= 1: the best legal move of a board after its spawn; 0 when it has none.  `leaves` counts
 // the A(., 0) evaluations below (< 2^32 per lane).  P = 1: the four after-states are evaluated side
 // by side, the 8 gathers of a tuple for every legal move issued before any is summed.
-template <int P, int K>
+template <int P, int K, bool S>
 __device__ __forceinline__ int64_t nts_M(const uint4 &b, const NtArgs &net, uint32_t &leaves) {
     long long best = kIllegal;
     if constexpr (P == 1) {
         uint64_t x[4];
+        uint32_t row[4];
         long long v[4];
         bool ok[4];
 #pragma unroll
@@ -72,14 +73,15 @@ __device__ __forceinline__ int64_t nts_M(const uint4 &b, const NtArgs &net, uint
             const uint4 s = apply_move(b, a, pts, mx);
             ok[a] = !eq4(s, b);
             x[a] = nt_pack(s);
+            row[a] = nt_row<S>(net, x[a]);  // each after-state at its own stage
             v[a] = gain_of(pts);
             leaves += ok[a] ? 1u : 0u;
         }
         for (int t = 0; t < net.T; t++) {
-            const int32_t *W = net.w + ((size_t)t << (4 * K));
             int32_t w[4][8];
 #pragma unroll
             for (int a = 0; a < 4; a++) {
+                const int32_t *W = net.w + ((size_t)(row[a] + t) << (4 * K));
 #pragma unroll
                 for (int g = 0; g < 8; g++) w[a][g] = ok[a] ? W[nt_index<K>(x[a], net.cells[8 * t + g])] : 0;
             }
@@ -97,7 +99,7 @@ __device__ __forceinline__ int64_t nts_M(const uint4 &b, const NtArgs &net, uint
             uint32_t pts, mx;
             const uint4 s = apply_move(b, a, pts, mx);
             if (eq4(s, b)) continue;
-            const long long v = gain_of(pts) + nts_A<P - 1, K>(s, net, leaves);
+            const long long v = gain_of(pts) + nts_A<P - 1, K, S>(s, net, leaves);
             best = v > best ? v : best;
         }
     }
@@ -105,11 +107,11 @@ __device__ __forceinline__ int64_t nts_M(const uint4 &b, const NtArgs &net, uint
 }
 
 // A(s, P) of an after-state: the weighted sum over every empty cell and both tiles, one floor division
-template <int P, int K>
+template <int P, int K, bool S>
 __device__ __forceinline__ int64_t nts_A(const uint4 &s, const NtArgs &net, uint32_t &leaves) {
     if constexpr (P == 0) {
         leaves += 1u;
-        return nt_value<K>(net, nt_pack(s));
+        return nt_value<K, S>(net, nt_pack(s));
     } else {
         uint32_t em = empty_mask16(s);
         const uint32_t E = (uint32_t)__popc(em);
@@ -122,7 +124,7 @@ __device__ __forceinline__ int64_t nts_A(const uint4 &s, const NtArgs &net, uint
             for (uint32_t t = 1u; t <= 2u; t++) {
                 uint4 child = s;
                 set_cell(child, c, t);
-                const int64_t m = nts_M<P, K>(child, net, leaves);
+                const int64_t m = nts_M<P, K, S>(child, net, leaves);
                 sum += t == 1u ? 9 * m : m;
             }
         }
@@ -142,7 +144,7 @@ __device__ __forceinline__ void group_sum32(uint64_t &x, uint64_t &l) {
 
 // the weighted value of the spawn j = 2 cell + (tile - 1) on the after-state s and its leaf count:
 // 9 M or 1 M of the child for an empty cell, nothing for an occupied one or a dead group
-template <int P, int K>
+template <int P, int K, bool S>
 __device__ __forceinline__ void spawn_lane(const uint4 &s, uint32_t em, bool group_live, uint32_t j, const NtArgs &net,
                                            uint64_t &x, uint64_t &l) {
     const uint32_t cell = j >> 1, tile = (j & 1u) + 1u;
@@ -152,7 +154,7 @@ __device__ __forceinline__ void spawn_lane(const uint4 &s, uint32_t em, bool gro
         uint4 child = s;
         set_cell(child, cell, tile);
         uint32_t lv = 0u;
-        const int64_t m = nts_M<P, K>(child, net, lv);
+        const int64_t m = nts_M<P, K, S>(child, net, lv);
         x = (uint64_t)(tile == 1u ? 9 * m : m);
         l = lv;
     }
@@ -181,7 +183,7 @@ __device__ __forceinline__ void write_legal_best(const long long (&v)[4], uint32
 // groups per wave.  For D >= 2 a live lane (legal a, empty cell) evaluates M(child, D - 1); the group's
 // 32 lanes are summed by shuffles, divided once and the move's points added.  D = 1 has no spawn
 // level: lane j = 0 of a legal action evaluates V.  Lane 0 then derives legal / best through LDS.
-template <int D, int K>
+template <int D, int K, bool S>
 __global__ __launch_bounds__(128) void nts_narrow_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                          long long *__restrict__ q_out, long long *__restrict__ leaves,
                                                          uint8_t *__restrict__ legal_out,
@@ -196,13 +198,13 @@ __global__ __launch_bounds__(128) void nts_narrow_kernel(NtArgs net, const uint4
     uint64_t l = 0ull;
     if constexpr (D == 1) {
         if (legal && j == 0u) {
-            v = gain_of(pts) + nt_value<K>(net, nt_pack(moved));
+            v = gain_of(pts) + nt_value<K, S>(net, nt_pack(moved));
             l = 1ull;
         }
     } else {
         const uint32_t em = empty_mask16(moved);
         uint64_t x;
-        spawn_lane<D - 1, K>(moved, em, legal, j, net, x, l);
+        spawn_lane<D - 1, K, S>(moved, em, legal, j, net, x, l);
         group_sum32(x, l);
         if (legal) v = gain_of(pts) + floor_div10e((int64_t)x, (uint32_t)__popc(em));
     }
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(128) void nts_narrow_kernel(NtArgs net, const uint4
 // then arrives at the (i, a) counter, as emax_wide_kernel does.  The last of the 32 arrivals divides,
 // adds the move's points and writes q / leaves; the last of a board's four writes legal / best.  A
 // workgroup of an illegal action or an occupied cell only arrives.
-template <int D, int K>
+template <int D, int K, bool S>
 __global__ __launch_bounds__(128) void nts_wide_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                        long long *__restrict__ q_out, long long *__restrict__ leaves,
                                                        uint8_t *__restrict__ legal_out, uint8_t *__restrict__ best_out,
@@ -256,13 +258,13 @@ __global__ __launch_bounds__(128) void nts_wide_kernel(NtArgs net, const uint4 *
         const bool legal2 = !eq4(moved2, b1);
         if constexpr (D == 2) {
             if (legal2 && j2 == 0u) {
-                q = gain_of(pts2) + nt_value<K>(net, nt_pack(moved2));
+                q = gain_of(pts2) + nt_value<K, S>(net, nt_pack(moved2));
                 l = 1ull;
             }
         } else {
             const uint32_t em2 = empty_mask16(moved2);
             uint64_t x;
-            spawn_lane<D - 2, K>(moved2, em2, legal2, j2, net, x, l);
+            spawn_lane<D - 2, K, S>(moved2, em2, legal2, j2, net, x, l);
             group_sum32(x, l);
             if (legal2) q = gain_of(pts2) + floor_div10e((int64_t)x, (uint32_t)__popc(em2));
         }
@@ -341,18 +343,18 @@ size_t workspace_bytes(int64_t n, int form) {
     return ((size_t)n * (4 * 8 + 4 * 8 + 4 * 4 + 4) + 15) & ~(size_t)15;
 }
 
-template <int D, int K>
+template <int D, int K, bool S>
 void launch_narrow(hipStream_t st, int64_t n, const NtArgs &a, const uint4 *b, long long *q, long long *lv,
                    uint8_t *legal, uint8_t *best) {
-    hipLaunchKernelGGL((nts_narrow_kernel<D, K>), dim3((unsigned)n), dim3(128), 0, st, a, b, q, lv, legal, best);
+    hipLaunchKernelGGL((nts_narrow_kernel<D, K, S>), dim3((unsigned)n), dim3(128), 0, st, a, b, q, lv, legal, best);
 }
 
-template <int D, int K>
+template <int D, int K, bool S>
 void launch_wide(hipStream_t st, int64_t n, const NtArgs &a, const uint4 *b, long long *q, long long *lv,
                  uint8_t *legal, uint8_t *best, void *workspace) {
     unsigned long long *ws_sum = (unsigned long long *)workspace, *ws_leaves = ws_sum + 4 * n;
     uint32_t *arrived_g = (uint32_t *)(ws_leaves + 4 * n), *arrived_b = arrived_g + 4 * n;
-    hipLaunchKernelGGL((nts_wide_kernel<D, K>), dim3((unsigned)(n * 128)), dim3(128), 0, st, a, b, q, lv, legal, best,
+    hipLaunchKernelGGL((nts_wide_kernel<D, K, S>), dim3((unsigned)(n * 128)), dim3(128), 0, st, a, b, q, lv, legal, best,
                        ws_sum, ws_leaves, arrived_g, arrived_b);
 }
 
@@ -365,11 +367,11 @@ size_t g2048_ntuple_search_workspace_bytes(int64_t n, int64_t depth, int32_t for
     return f < 0 ? 0 : workspace_bytes(n < 1 ? 1 : n, f);
 }
 
-int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t n,
+static int nt_call_search(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, const int8_t *boards, int64_t n,
                         int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal, uint8_t *best,
                         void *workspace, size_t workspace_bytes_in) {
     NtArgs a;
-    if (!make_args(net, a)) return G2048_EINVAL;
+    if (!make_args(net, stage_map, a)) return G2048_EINVAL;
     const int f = resolve_form(n, depth, form);
     if (f < 0) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
@@ -381,9 +383,9 @@ int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, cons
     long long *qv = (long long *)q, *lv = (long long *)leaves;
     if (f == G2048_EMAX_NARROW) {
         switch (depth) {
-        case 1: G2048_NT_DISPATCH(net->tuple_len, (launch_narrow<1, kK>(st, n, a, b, qv, lv, legal, best))); break;
-        case 2: G2048_NT_DISPATCH(net->tuple_len, (launch_narrow<2, kK>(st, n, a, b, qv, lv, legal, best))); break;
-        default: G2048_NT_DISPATCH(net->tuple_len, (launch_narrow<3, kK>(st, n, a, b, qv, lv, legal, best))); break;
+        case 1: G2048_NT_DISPATCH(a, net->tuple_len, (launch_narrow<1, kK, kS>(st, n, a, b, qv, lv, legal, best))); break;
+        case 2: G2048_NT_DISPATCH(a, net->tuple_len, (launch_narrow<2, kK, kS>(st, n, a, b, qv, lv, legal, best))); break;
+        default: G2048_NT_DISPATCH(a, net->tuple_len, (launch_narrow<3, kK, kS>(st, n, a, b, qv, lv, legal, best))); break;
         }
         return launch_status();
     }
@@ -392,11 +394,24 @@ int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, cons
     const int zs = launch_status();
     if (zs != G2048_OK) return zs;
     if (depth == 2) {
-        G2048_NT_DISPATCH(net->tuple_len, (launch_wide<2, kK>(st, n, a, b, qv, lv, legal, best, workspace)));
+        G2048_NT_DISPATCH(a, net->tuple_len, (launch_wide<2, kK, kS>(st, n, a, b, qv, lv, legal, best, workspace)));
     } else {
-        G2048_NT_DISPATCH(net->tuple_len, (launch_wide<3, kK>(st, n, a, b, qv, lv, legal, best, workspace)));
+        G2048_NT_DISPATCH(a, net->tuple_len, (launch_wide<3, kK, kS>(st, n, a, b, qv, lv, legal, best, workspace)));
     }
     return launch_status();
+}
+
+// the entry points: the one-stage call is its twin on a staged net with the map 0
+int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t n,
+                        int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal, uint8_t *best,
+                        void *workspace, size_t workspace_bytes) {
+    return nt_call_search(stream, net, 0, boards, n, depth, form, q, leaves, legal, best, workspace, workspace_bytes);
+}
+int g2048_ntuple_staged_search(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                               int64_t n, int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal,
+                               uint8_t *best, void *workspace, size_t workspace_bytes) {
+    return nt_call_search(stream, net ? &net->net : nullptr, net ? net->stage_map : 0, boards, n, depth, form, q, leaves,
+                          legal, best, workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ _STRUCT_NAMES = {
     "g2048_rng": "Rng",
     "g2048_reward_cfg": "RewardCfg",
     "g2048_ntuple_net": "NtNet",
+    "g2048_ntuple_staged_net": "NtStagedNet",
     "g2048_dropout": "Dropout",
     "g2048_policy_rollout_args": "PolicyRolloutArgs",
     "g2048_colsum_job": "ColsumJob",
@@ -295,40 +296,85 @@ def expectimax(boards, depth: int, weights, value, leaves=None, legal=None, best
           workspace.numel())
 
 
-def make_ntuple_net(cells, weights: torch.Tensor) -> NtNet:
+def make_ntuple_net(cells, weights: torch.Tensor, stage_map: int = 0):
     """The host struct of an n-tuple network: cells = T tuples of K cell indices (4 row + col), weights the
-    device int32 tensor of its T x 16^K table entries.  Raises for a net the library would refuse."""
+    device int32 tensor of its table entries.  stage_map 0: an NtNet, the one-stage net of T x 16^K weights.
+    Otherwise an NtStagedNet of G x T x 16^K weights, stage_map the stage of every largest exponent: every
+    ntuple_* wrapper below takes either and calls the entry point of its kind.  Raises for a net the library
+    would refuse."""
     cells = [[int(c) for c in tup] for tup in cells]
     T, K = len(cells), len(cells[0]) if cells else 0
     if not 1 <= T <= NT_MAX_TUPLES or not 1 <= K <= NT_MAX_LEN or any(len(tup) != K for tup in cells):
         raise G2048Error(f"ntuple: 1..{NT_MAX_TUPLES} tuples of one length in 1..{NT_MAX_LEN}, got {cells}")
     flat = [c for tup in cells for c in tup]
+    stage_map = int(stage_map)
+    if not 0 <= stage_map < 1 << 64:
+        raise G2048Error(f"ntuple: stage_map must fit 64 bits, got {stage_map}")
     net = NtNet(T, K, (ctypes.c_int32 * (NT_MAX_TUPLES * NT_MAX_LEN))(*flat), _dev(weights, torch.int32, "weights"))
-    count = int(load().g2048_ntuple_weight_count(ctypes.byref(net)))
+    if stage_map == 0:
+        count = int(load().g2048_ntuple_weight_count(ctypes.byref(net)))
+    else:
+        net = NtStagedNet(net, stage_map)
+        count = int(load().g2048_ntuple_staged_weight_count(ctypes.byref(net)))
     if count == 0:
-        raise G2048Error(f"ntuple: cells {cells} are refused (0..15, distinct within a tuple; weights 16-B aligned)")
+        raise G2048Error(f"ntuple: cells {cells} or stage_map {stage_map:#x} are refused (cells 0..15, distinct "
+                         f"within a tuple; weights 16-B aligned; stages from 0, each the one before or one more)")
     if weights.numel() != count:
         raise G2048Error(f"ntuple: weights hold {weights.numel()} elements, the net needs {count}")
     return net
 
 
-def ntuple_value(net: NtNet, boards, value):
+def _nt_entry(net, call: str) -> str:
+    """The entry point `call` for the kind of net: g2048_ntuple_<call> or its twin on a staged net."""
+    return f"g2048_ntuple_staged_{call}" if isinstance(net, NtStagedNet) else f"g2048_ntuple_{call}"
+
+
+def _ntuple_weight_count(net) -> int:
+    """G x T x 16^K of a net make_ntuple_net accepted."""
+    if isinstance(net, NtStagedNet):
+        return (1 + (net.stage_map >> 60)) * (net.net.num_tuples << (4 * net.net.tuple_len))
+    return net.num_tuples << (4 * net.tuple_len)
+
+
+def _staged(net) -> NtStagedNet:
+    """The net as the staged entry points take it: a one-stage NtNet is the staged net with the map 0."""
+    return net if isinstance(net, NtStagedNet) else NtStagedNet(net, 0)
+
+
+def ntuple_stage(net, boards, out):
+    """out uint8 [n] = stage(boards[i]) (g2048_ntuple_stage)."""
+    n = boards.shape[0]
+    if out is None or out.numel() < n:
+        raise G2048Error(f"ntuple_stage: out holds {None if out is None else out.numel()} elements, needs {n}")
+    _call("g2048_ntuple_stage", _stream(boards), ctypes.byref(_staged(net)), _dev(boards, torch.int8, "boards"),
+          _dev(out, torch.uint8, "out"), n)
+
+
+def ntuple_promote(net, src: int, dst: int, device=None):
+    """W[dst] += W[src], the tables of two stages of the net (g2048_ntuple_promote), on torch's current stream
+    of `device` (the device of the net's weights; None: the current device)."""
+    _call("g2048_ntuple_promote", ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream),
+          ctypes.byref(_staged(net)),
+          int(src), int(dst))
+
+
+def ntuple_value(net, boards, value):
     """value int64 [n] = V(boards[i]) (g2048_ntuple_value)."""
     n = boards.shape[0]
     if value.numel() < n:
         raise G2048Error(f"ntuple_value: value holds {value.numel()} elements, needs {n}")
-    _call("g2048_ntuple_value", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+    _call(_nt_entry(net, "value"), _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
           _dev(value, torch.int64, "value"), n)
 
 
-def ntuple_choose(net: NtNet, boards, q=None, legal=None, best=None):
+def ntuple_choose(net, boards, q=None, legal=None, best=None):
     """The greedy choice (g2048_ntuple_choose): q int64 [n, 4] (INT64_MIN: illegal), legal / best uint8 [n];
     each optional, not all three."""
     n = boards.shape[0]
     for t, nm, k in ((q, "q", 4 * n), (legal, "legal", n), (best, "best", n)):
         if t is not None and t.numel() < k:
             raise G2048Error(f"ntuple_choose: {nm} holds {t.numel()} elements, needs {k}")
-    _call("g2048_ntuple_choose", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+    _call(_nt_entry(net, "choose"), _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
           _dev(q, torch.int64, "q"), _dev(legal, torch.uint8, "legal"), _dev(best, torch.uint8, "best"), n)
 
 
@@ -337,7 +383,7 @@ def ntuple_search_workspace_bytes(n: int, depth: int, form: int = EMAX_AUTO) -> 
     return int(load().g2048_ntuple_search_workspace_bytes(int(n), int(depth), int(form)))
 
 
-def ntuple_search(net: NtNet, boards, depth: int, q, leaves=None, legal=None, best=None, workspace=None,
+def ntuple_search(net, boards, depth: int, q, leaves=None, legal=None, best=None, workspace=None,
                   form: int = EMAX_AUTO):
     """Expectimax search with the net at the leaves (g2048_ntuple_search): boards int8 [n, 16] -> q int64
     [n, 4] (INT64_MIN: illegal), leaves int64 [n, 4], legal / best uint8 [n] (the last three optional).
@@ -352,7 +398,7 @@ def ntuple_search(net: NtNet, boards, depth: int, q, leaves=None, legal=None, be
     if workspace is None:
         raise G2048Error("ntuple_search: a workspace of ntuple_search_workspace_bytes(n, depth, form) bytes "
                          "is required")
-    _call("g2048_ntuple_search", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"), n, int(depth),
+    _call(_nt_entry(net, "search"), _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"), n, int(depth),
           int(form), _dev(q, torch.int64, "q"), _dev(leaves, torch.int64, "leaves"), _dev(legal, torch.uint8, "legal"),
           _dev(best, torch.uint8, "best"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
 
@@ -362,7 +408,7 @@ def ntuple_td_workspace_bytes(n: int) -> int:
     return int(load().g2048_ntuple_td_workspace_bytes(int(n)))
 
 
-def ntuple_td(net: NtNet, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
+def ntuple_td(net, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
               workspace=None):
     """`steps` afterstate TD(0) steps of the n envs on one net (g2048_ntuple_td): boards / after int8 [n, 16],
     pending uint8 [n], run_score int64 [n] carried; stats int64 [4] accumulated (optional); workspace: a
@@ -373,7 +419,7 @@ def ntuple_td(net: NtNet, boards, after, pending, run_score, steps: int, lr_shif
             raise G2048Error(f"ntuple_td: {nm} holds {t.numel()} elements, needs {k}")
     if workspace is None:
         raise G2048Error("ntuple_td: a workspace of ntuple_td_workspace_bytes(n) bytes is required")
-    _call("g2048_ntuple_td", _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
+    _call(_nt_entry(net, "td"), _stream(boards), ctypes.byref(net), _dev(boards, torch.int8, "boards"),
           _dev(after, torch.int8, "after"), _dev(pending, torch.uint8, "pending"),
           _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), ctypes.byref(rng),
           _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
@@ -384,13 +430,13 @@ def ntuple_tc_workspace_bytes(n: int) -> int:
     return int(load().g2048_ntuple_tc_workspace_bytes(int(n)))
 
 
-def ntuple_tc(net: NtNet, tc, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
+def ntuple_tc(net, tc, boards, after, pending, run_score, steps: int, lr_shift: int, rng: Rng, stats=None,
               workspace=None):
     """`steps` temporal-coherence steps of the n envs on one net (g2048_ntuple_tc): ntuple_td's arguments and
-    tc, the int64 device tensor [T, 16^K, 2] of the accumulators (E, A) of the net's weights, on the
+    tc, the int64 device tensor [G, T, 16^K, 2] of the accumulators (E, A) of the net's weights, on the
     device of boards; workspace: a uint8 device tensor of ntuple_tc_workspace_bytes(n) bytes."""
     n = boards.shape[0]
-    count = 2 * (net.num_tuples << (4 * net.tuple_len))  # two int64 per weight
+    count = 2 * _ntuple_weight_count(net)  # two int64 per weight
     if tc is None or tc.dtype != torch.int64 or tc.numel() != count or tc.device != boards.device:
         raise G2048Error(f"ntuple_tc: tc must be int64 with {count} elements on {boards.device}, got "
                          f"{None if tc is None else (tc.dtype, tc.numel(), tc.device)}")
@@ -399,7 +445,7 @@ def ntuple_tc(net: NtNet, tc, boards, after, pending, run_score, steps: int, lr_
             raise G2048Error(f"ntuple_tc: {nm} holds {t.numel()} elements, needs {k}")
     if workspace is None:
         raise G2048Error("ntuple_tc: a workspace of ntuple_tc_workspace_bytes(n) bytes is required")
-    _call("g2048_ntuple_tc", _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
+    _call(_nt_entry(net, "tc"), _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
           _dev(boards, torch.int8, "boards"), _dev(after, torch.int8, "after"), _dev(pending, torch.uint8, "pending"),
           _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), ctypes.byref(rng),
           _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"), workspace.numel())
@@ -410,7 +456,7 @@ def ntuple_lambda_workspace_bytes(n: int) -> int:
     return int(load().g2048_ntuple_lambda_workspace_bytes(int(n)))
 
 
-def ntuple_lambda(net: NtNet, tc, boards, after, hist, hist_len, pending, run_score, steps: int, lr_shift: int,
+def ntuple_lambda(net, tc, boards, after, hist, hist_len, pending, run_score, steps: int, lr_shift: int,
                   trace_len: int, lambda_shift: int, rng: Rng, stats=None, workspace=None):
     """`steps` TD(lambda) (tc None) or TC(lambda) steps of the n envs on one net (g2048_ntuple_lambda), lambda =
     2^-lambda_shift over a trace of trace_len after-states: ntuple_td's arguments, tc as ntuple_tc's or None,
@@ -418,7 +464,7 @@ def ntuple_lambda(net: NtNet, tc, boards, after, hist, hist_len, pending, run_sc
     trace_len 0); workspace: a uint8 device tensor of ntuple_lambda_workspace_bytes(n) bytes."""
     n, trace_len = boards.shape[0], int(trace_len)
     if tc is not None:
-        count = 2 * (net.num_tuples << (4 * net.tuple_len))  # two int64 per weight
+        count = 2 * _ntuple_weight_count(net)  # two int64 per weight
         if tc.dtype != torch.int64 or tc.numel() != count or tc.device != boards.device:
             raise G2048Error(f"ntuple_lambda: tc must be int64 with {count} elements on {boards.device}, got "
                              f"{(tc.dtype, tc.numel(), tc.device)}")
@@ -430,7 +476,7 @@ def ntuple_lambda(net: NtNet, tc, boards, after, hist, hist_len, pending, run_sc
             raise G2048Error(f"ntuple_lambda: {nm} holds {t.numel()} elements, needs {k}")
     if workspace is None:
         raise G2048Error("ntuple_lambda: a workspace of ntuple_lambda_workspace_bytes(n) bytes is required")
-    _call("g2048_ntuple_lambda", _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
+    _call(_nt_entry(net, "lambda"), _stream(boards), ctypes.byref(net), _dev(tc, torch.int64, "tc"),
           _dev(boards, torch.int8, "boards"), _dev(after, torch.int8, "after"), _dev(hist, torch.int8, "hist"),
           _dev(hist_len, torch.uint8, "hist_len"), _dev(pending, torch.uint8, "pending"),
           _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), trace_len, int(lambda_shift),

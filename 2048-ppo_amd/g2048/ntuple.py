@@ -9,7 +9,9 @@ maximum; the updates are integer adds, so a run is reproducible bit for bit.  Wi
 weight sets its own step size from the sums of its past updates (temporal-coherence learning,
 g2048_ntuple_tc), integer too.  With trace_len > 0 the error of an after-state is also passed back, halved
 (or shifted by lambda_shift) per move, to the trace_len after-states before it: TD(lambda) / TC(lambda) with
-lambda = 2^-lambda_shift (g2048_ntuple_lambda).  NTuplePlayer: the greedy
+lambda = 2^-lambda_shift (g2048_ntuple_lambda).  With `stages` a net keeps one set of tables per stage of
+the game, the stage of a board given by its largest tile (Yeh et al. 2016; Jaskowski 2018), and the trainer's
+promote_every starts every stage from the tables of the one below it.  NTuplePlayer: the greedy
 player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
 search.py's game loop.
 """
@@ -29,6 +31,7 @@ MAX_TUPLES, MAX_LEN, FRAC_BITS = L.NT_MAX_TUPLES, L.NT_MAX_LEN, L.NT_FRAC_BITS
 MAX_ENVS = (1 << 28) - 1
 MAX_SEARCH_DEPTH = 3
 MAX_TRACE, MAX_LAMBDA_SHIFT = L.NT_MAX_TRACE, L.NT_MAX_LAMBDA_SHIFT
+MAX_STAGES = L.NT_MAX_STAGES
 
 
 def _check_cells(cells) -> list[list[int]]:
@@ -48,14 +51,34 @@ def _check_cells(cells) -> list[list[int]]:
     return cells
 
 
-class NTupleNet:
-    """cells: a preset name or T tuples of K cell indices (4 row + col).  weights: int32 [T, 16^K] on
-    `device`, zero at the start (the greedy-on-points player)."""
+def _check_stages(stages) -> tuple[int, ...]:
+    stages = tuple(int(v) for v in stages)
+    if any(v < 2 or v > 32768 or v & (v - 1) for v in stages) or any(a >= b for a, b in zip(stages, stages[1:])):
+        raise ValueError(f"stages are strictly increasing tile values, each a power of two in 2..32768, got {stages}")
+    return stages
 
-    def __init__(self, cells="lines-squares-4", device="cuda", weights: torch.Tensor | None = None):
+
+def stage_map_of(stages) -> int:
+    """The stage_map of g2048_ntuple_net for a list of tile values: nibble m = the number of listed tiles that
+    are <= 2^m (exponent 15 stands for every larger tile too); 0 for no stages."""
+    stages = _check_stages(stages)
+    return sum(sum(1 for v in stages if v <= 1 << m) << (4 * m) for m in range(1, 16))
+
+
+class NTupleNet:
+    """cells: a preset name or T tuples of K cell indices (4 row + col).  stages: strictly increasing tile
+    values (powers of two in 2..32768); the stage of a board is the number of them that are <= its largest
+    tile, and every stage has tables of its own (G = len(stages) + 1 of them).  weights: int32 [T, 16^K]
+    without stages, [G, T, 16^K] with them, on `device`, zero at the start (the greedy-on-points player)."""
+
+    def __init__(self, cells="lines-squares-4", device="cuda", weights: torch.Tensor | None = None, stages=()):
         self.cells = _check_cells(cells)
         self.device = torch.device(device)
+        self.stages = _check_stages(stages)
+        self.stage_map = stage_map_of(self.stages)
         shape = (len(self.cells), 16 ** len(self.cells[0]))
+        if self.stages:
+            shape = (len(self.stages) + 1,) + shape
         if weights is None:
             weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
         else:
@@ -66,11 +89,29 @@ class NTupleNet:
         self._c = None
 
     @property
-    def c(self) -> L.NtNet:
-        """The host struct the library reads (the first use needs the device)."""
+    def c(self):
+        """The host struct the library reads (the first use needs the device): an L.NtNet, or an L.NtStagedNet
+        for a net with stages."""
         if self._c is None:
-            self._c = L.make_ntuple_net(self.cells, self.weights)
+            self._c = L.make_ntuple_net(self.cells, self.weights, self.stage_map)
         return self._c
+
+    @property
+    def num_stages(self) -> int:
+        return len(self.stages) + 1
+
+    def stage(self, boards: torch.Tensor) -> torch.Tensor:
+        """The stage of boards int8 [n, 16] -> uint8 [n]."""
+        out = torch.empty(boards.shape[0], dtype=torch.uint8, device=boards.device)
+        L.ntuple_stage(self.c, boards, out)
+        return out
+
+    def promote(self, src: int, dst: int) -> None:
+        """Adds the tables of stage src to those of stage dst (int32, wrapping): a copy onto a zero stage."""
+        src, dst = int(src), int(dst)
+        if not (0 <= src < self.num_stages and 0 <= dst < self.num_stages) or src == dst:
+            raise ValueError(f"promote needs two different stages in 0..{self.num_stages - 1}, got {src} -> {dst}")
+        L.ntuple_promote(self.c, src, dst, self.device)
 
     def value(self, boards: torch.Tensor) -> torch.Tensor:
         """V of boards int8 [n, 16] -> int64 [n] (points x 4096)."""
@@ -79,12 +120,16 @@ class NTupleNet:
         return out
 
     def save(self, path) -> None:
-        torch.save({"cells": self.cells, "weights": self.weights.cpu()}, path)
+        """cells and weights, and for a net with stages the key "stages"; a one-stage checkpoint is unchanged."""
+        ck = {"cells": self.cells, "weights": self.weights.cpu()}
+        if self.stages:
+            ck["stages"] = list(self.stages)
+        torch.save(ck, path)
 
     @classmethod
     def load(cls, path, device="cuda") -> "NTupleNet":
         ck = torch.load(path, map_location="cpu", weights_only=True)
-        return cls(ck["cells"], device, ck["weights"])
+        return cls(ck["cells"], device, ck["weights"], ck.get("stages", ()))
 
 
 class NTupleTrainer:
@@ -101,13 +146,24 @@ class NTupleTrainer:
     an update's D is also applied, shifted right by k lambda_shift (towards zero), to the after-state k
     moves older of the same game, k = 1..trace_len (self.hist int8 [trace_len, envs, 16], self.hist_len
     uint8 [envs]); a game's end reaches the trace of that game, and a new game starts an empty one.
-    trace_len 0 is exactly the calls above, whatever lambda_shift is."""
+    trace_len 0 is exactly the calls above, whatever lambda_shift is.
+    promote_every P > 0 (a net with stages only): the trainer cuts its step sequence at every multiple of P
+    steps since its start, however train() is called; at a cut it reads the highest stage g* any of its
+    boards is in and promotes g - 1 -> g for every g in promoted_upto + 1 .. g*, in ascending order.  So every
+    stage is promoted once, from the stage below it, the first time a cut sees a board at or above it;
+    what the stage learned before that cut is kept, since promotion adds.  The accumulators of rule "tc"
+    are not promoted.  0: never, exactly the calls above."""
 
     RULES = ("td", "tc")
 
     def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td",
-                 trace_len: int = 0, lambda_shift: int = 1):
+                 trace_len: int = 0, lambda_shift: int = 1, promote_every: int = 0):
         envs, lr_shift, trace_len, lambda_shift = int(envs), int(lr_shift), int(trace_len), int(lambda_shift)
+        promote_every = int(promote_every)
+        if promote_every < 0:
+            raise ValueError(f"promote_every must not be negative, got {promote_every}")
+        if promote_every > 0 and not net.stages:
+            raise ValueError("promote_every needs a net with stages")
         if not 1 <= envs <= MAX_ENVS:
             raise ValueError(f"envs must be in [1, {MAX_ENVS}], got {envs}")
         if not 1 <= lr_shift <= 30:
@@ -120,6 +176,7 @@ class NTupleTrainer:
             raise ValueError(f"lambda_shift must be in [1, {MAX_LAMBDA_SHIFT}], got {lambda_shift}")
         self.net, self.envs, self.lr_shift, self.seed, self.rule = net, envs, lr_shift, int(seed), rule
         self.trace_len, self.lambda_shift = trace_len, lambda_shift
+        self.promote_every, self.promoted_upto = promote_every, 0
         self.counter = 0
         self.boards = None
         self.tc = None
@@ -144,16 +201,7 @@ class NTupleTrainer:
         L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
         self.counter = 1
 
-    @torch.no_grad()
-    def train(self, steps: int) -> dict:
-        """`steps` more TD steps of every env -> the statistics of these steps: games finished, their
-        mean and largest score (0 without a finished game) and the updates applied."""
-        steps = int(steps)
-        if steps < 1:
-            raise ValueError(f"steps must be positive, got {steps}")
-        if self.boards is None:
-            self._start()
-        self.stats.zero_()
+    def _steps(self, steps: int) -> None:
         rng = L.make_rng(L.RNG_PHILOX, self.seed, self.counter)
         if self.trace_len > 0:
             L.ntuple_lambda(self.net.c, self.tc, self.boards, self.after, self.hist, self.hist_len, self.pending,
@@ -166,12 +214,39 @@ class NTupleTrainer:
             L.ntuple_td(self.net.c, self.boards, self.after, self.pending, self.run_score, steps, self.lr_shift, rng,
                         self.stats, self.workspace)
         self.counter += steps
+
+    def _cut(self) -> list[int]:
+        """A cut of promote_every: promotes the stages up to the highest one a board is in, each once."""
+        top = int(self.net.stage(self.boards).max())  # a host read
+        promoted = list(range(self.promoted_upto + 1, top + 1))
+        for g in promoted:
+            self.net.promote(g - 1, g)
+        self.promoted_upto = max(self.promoted_upto, top)
+        return promoted
+
+    @torch.no_grad()
+    def train(self, steps: int) -> dict:
+        """`steps` more TD steps of every env -> the statistics of these steps: games finished, their
+        mean and largest score (0 without a finished game), the updates applied and the stages promoted."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps must be positive, got {steps}")
+        if self.boards is None:
+            self._start()
+        self.stats.zero_()
+        promoted, P = [], self.promote_every
+        while steps > 0:
+            k = min(steps, P - (self.counter - 1) % P) if P > 0 else steps  # counter - 1 steps since the start
+            self._steps(k)
+            steps -= k
+            if P > 0 and (self.counter - 1) % P == 0:
+                promoted += self._cut()
         games, score_sum, best, updates = self.stats.tolist()
         return {"games": games, "mean_score": score_sum / games if games else 0.0, "max_score": best,
-                "updates": updates, "score_sum": score_sum}
+                "updates": updates, "score_sum": score_sum, "promoted": promoted}
 
     def accumulators(self):
-        """-> (E, A): views int64 [T, 16^K] of a weight's signed and absolute update sums under rule "tc" (A
+        """-> (E, A): views int64 [T, 16^K] ([G, T, 16^K] with stages) of a weight's signed and absolute update sums under rule "tc" (A
         is unsigned: read its int64 as uint64); None, None before the first train()."""
         if self.rule != "tc":
             raise ValueError('only rule "tc" keeps accumulators')

@@ -405,12 +405,22 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
                                                               "truncated trace; 0: TD(0) / TC"),
                  lambda_shift: int = typer.Option(1, "--lambda-shift", help="lambda = 2^-S, S in 1..7: the update "
                                                                             "of the after-state k moves older is "
-                                                                            "shifted right by k S")):
+                                                                            "shifted right by k S"),
+                 stages: str = typer.Option("", "--stages", help="tile values, e.g. 2048,4096,8192: one set of "
+                                                                 "tables per stage of the game, the stage of a "
+                                                                 "board = how many of them its largest tile has "
+                                                                 "reached; empty: one stage"),
+                 promote_every: int = typer.Option(0, "--promote-every", help="every P steps, start each stage a "
+                                                                              "board has newly reached from the "
+                                                                              "tables of the stage below it (needs "
+                                                                              "--stages); 0: never")):
     """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
     reproducible bit for bit.  Prints the games finished and their mean score per interval.  --rule tc
     keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, so resuming a TC
     run from a saved net is out of scope.  --trace H passes every error back along the last H
-    after-states of its game, decayed by lambda = 2^-S (--lambda-shift S), under either rule."""
+    after-states of its game, decayed by lambda = 2^-S (--lambda-shift S), under either rule.  --stages
+    gives the net tables of its own for every stage of the game; --promote-every P adds, once per stage,
+    the tables of the stage below to it."""
     from g2048.ntuple import MAX_LAMBDA_SHIFT, MAX_TRACE, PRESETS, NTupleNet, NTupleTrainer
     if tuples not in PRESETS:
         typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
@@ -424,13 +434,26 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
     if not 1 <= lambda_shift <= MAX_LAMBDA_SHIFT:
         typer.echo(f"Error: --lambda-shift must be in 1..{MAX_LAMBDA_SHIFT}, got {lambda_shift}")
         raise typer.Exit(1)
+    try:
+        stage_list = [int(v) for v in stages.split(",") if v.strip()]
+    except ValueError:
+        stage_list = None
+    ok = stage_list is not None and all(2 <= v <= 32768 and v & (v - 1) == 0 for v in stage_list) and \
+        all(a < b for a, b in zip(stage_list, stage_list[1:]))
+    if not ok:
+        typer.echo(f"Error: --stages must be strictly increasing powers of two in 2..32768, got {stages}")
+        raise typer.Exit(1)
+    if promote_every < 0 or (promote_every > 0 and not stage_list):
+        typer.echo(f"Error: --promote-every must be 0, or positive with --stages, got {promote_every}")
+        raise typer.Exit(1)
     if not torch.cuda.is_available():
         typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
         raise typer.Exit(1)
-    net = NTupleNet(tuples, torch.device("cuda", 0))
-    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift)
+    net = NTupleNet(tuples, torch.device("cuda", 0), stages=stage_list)
+    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift, promote_every)
     typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
-               f"{net.weights.numel()} weights; {envs} envs, lr_shift {lr_shift}, trace {trace}, "
+               f"{net.weights.numel()} weights; stages {','.join(map(str, net.stages)) or 'none'}, "
+               f"promote_every {promote_every}; {envs} envs, lr_shift {lr_shift}, trace {trace}, "
                f"lambda_shift {lambda_shift}, rule {rule}")
     done = 0
     while done < steps:
@@ -438,7 +461,7 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
         st = tr.train(k)
         done += k
         typer.echo(f"step {done}: games {st['games']}, mean score {st['mean_score']:.1f}, max {st['max_score']}, "
-                   f"updates {st['updates']}")
+                   f"updates {st['updates']}" + (f", promoted {st['promoted']}" if st["promoted"] else ""))
     if out is not None:
         out.parent.mkdir(parents=True, exist_ok=True)
         net.save(out)

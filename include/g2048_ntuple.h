@@ -6,7 +6,7 @@
  * the call), asynchronous on `stream`, no allocation and no host synchronisation (hipGraph-capturable),
  * 0 / G2048_EINVAL (nothing enqueued) / a positive hipError_t, n = 0 a no-op.  This text is the
  * specification; tests/ntuple_reference.py restates it, tests/ntuple_tc_reference.py the TC step,
- * tests/ntuple_lambda_reference.py the lambda step.
+ * tests/ntuple_lambda_reference.py the lambda step, tests/ntuple_stage_reference.py the stages.
  *
  * The network.  T tuples of K cells each (cell = 4 row + col) and one table of 16^K int32 weights per
  * tuple.  All values are integers: points x S, S = 2^G2048_NT_FRAC_BITS = 4096.
@@ -123,6 +123,34 @@
  * Bound.  |V| <= 64 x 2^31 = 2^37; S pts < 2^31 per ply, so |M| < 2^38 for d <= 3; a chance node sums at
  * most 160 weighted terms, |sum| < 2^46.  The signed floor is the unsigned one of sum + 10 E 2^40
  * (< 2^48), minus 2^40: exact.  Depth 4 is out of scope.
+ *
+ * Stages (Yeh et al. 2016; Jaskowski 2018).  A game is not stationary: one pattern means different things
+ * on a board whose largest tile is 256 and on one that holds a 2048.  A staged net keeps one set of
+ * tables per stage of the game, and the stage of a board is a function of its largest tile:
+ *   m(b)     = max over the 16 cells c of e(b, c)       clamped to 15 like every exponent; 0: the empty board
+ *   stage(b) = nibble m(b) of stage_map                 bits 4 m .. 4 m + 3
+ *   G        = 1 + nibble 15 of stage_map               the number of stages, 1..G2048_NT_MAX_STAGES
+ * A map is valid when nibble 0 is 0 and every next nibble equals the one before it or is one more: the
+ * stages are numbered without gaps and never decrease as the largest tile grows.  stage_map == 0 is the
+ * one-stage net: every call then gives the results of the text above byte for byte.  m, and so the
+ * stage, is the same for the 8 symmetric images of a board.
+ * With stages, weights is int32 [G][T][16^K] and tc int64 [G][T][16^K][2], and
+ *   V(b) = sum over t < T and over the 8 symmetries g of W[stage(b)][t][idx_t(g(b))].
+ * "The 8 T weights that V(s) reads" are, wherever this text uses the phrase, those of stage(s): in the
+ * TD update of after[i], in the records of the TC step, and for every s_k of the lambda step, each at its
+ * own stage.  Nothing else changes in the choice, the three steps or the search.  In particular a target
+ * q[a*] may come from another stage's tables than those of the after-state being updated: that is the
+ * point of the method.  The leaves of the search evaluate V at the stage of each leaf after-state; its
+ * bounds hold unchanged, since a V still sums 8 T weights.
+ * Promotion (g2048_ntuple_promote) adds the tables of one stage to those of another, W[to][j] += W[from][j]
+ * for every j < T 16^K, int32 and wrapping like every add on the weights: on a zero stage it is a copy, so
+ * a stage can start from what the stage below it has learned instead of from nothing.  The accumulators
+ * of rule TC are not touched: a promoted stage starts with "never updated" records, at the base rate.
+ * The ABI.  g2048_ntuple_net and the calls that take it are unchanged: they are the one-stage net.  A net
+ * with stages is a g2048_ntuple_staged_net, the same struct followed by stage_map, and every call has a
+ * twin g2048_ntuple_staged_<call> that takes it and is otherwise the same call: the same arguments in the
+ * same order, the same refusals (and an invalid map), the same workspace.  With stage_map == 0 a twin is
+ * its one-stage call bit for bit.  C callers zero-initialise the struct (a designated initialiser does).
  */
 #ifndef G2048_NTUPLE_H
 #define G2048_NTUPLE_H
@@ -138,6 +166,7 @@ extern "C" {
 #define G2048_NT_FRAC_BITS 12 /* S = 4096: values are points x S */
 #define G2048_NT_MAX_TRACE 4        /* the longest eligibility trace of the lambda step */
 #define G2048_NT_MAX_LAMBDA_SHIFT 7 /* lambda = 2^-lambda_shift, lambda_shift in 1..7 */
+#define G2048_NT_MAX_STAGES 16      /* G, the number of stages of a net, is in 1..16 */
 
 typedef struct g2048_ntuple_net { /* host struct, read during the call */
     int32_t num_tuples;           /* T in 1..8 */
@@ -145,6 +174,11 @@ typedef struct g2048_ntuple_net { /* host struct, read during the call */
     int32_t cells[48];            /* cells[K t + j] = 4 row + col, 0..15; cells within a tuple distinct */
     int32_t *weights;             /* device int32 [T][16^K], 16-B aligned */
 } g2048_ntuple_net;
+
+typedef struct g2048_ntuple_staged_net { /* host struct, read during the call: a net with stages (Stages, above) */
+    g2048_ntuple_net net; /* as above, but weights is device int32 [G][T][16^K] */
+    uint64_t stage_map;   /* nibble m (bits 4 m ..) = the stage of a board whose largest clamped exponent is m; 0: one stage */
+} g2048_ntuple_staged_net;
 
 /* T x 16^K, the number of int32 weights; 0 for a net the calls below would refuse (a null net, T, K or
    a cell out of range, a repeated cell in a tuple, null or misaligned weights). */
@@ -219,6 +253,43 @@ size_t g2048_ntuple_search_workspace_bytes(int64_t n, int64_t depth, int32_t for
 int g2048_ntuple_search(g2048_stream_t stream, const g2048_ntuple_net *net, const int8_t *boards, int64_t n,
                         int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal, uint8_t *best,
                         void *workspace, size_t workspace_bytes);
+
+/* ---- nets with stages (Stages, above).  G x T x 16^K, the number of int32 weights of a staged net; 0 for a
+   net the calls below would refuse: what g2048_ntuple_weight_count refuses, and an invalid stage_map. */
+size_t g2048_ntuple_staged_weight_count(const g2048_ntuple_staged_net *net);
+
+/* stage[i] = stage(boards[i]), uint8 [n]: 0 for every board when stage_map == 0.  boards [n,16] is only
+   read.  0 <= n < 2^31.  G2048_EINVAL for a net g2048_ntuple_staged_weight_count refuses, n out of range,
+   null or misaligned boards, a null stage. */
+int g2048_ntuple_stage(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                       uint8_t *stage, int64_t n);
+
+/* Promotion (Stages, above): W[to][j] += W[from][j] for every j < T 16^K, one launch.  G2048_EINVAL for a
+   net g2048_ntuple_staged_weight_count refuses, from or to outside 0..G-1, from == to. */
+int g2048_ntuple_promote(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int32_t from, int32_t to);
+
+/* The twins of the calls above on a staged net: each is its one-stage call with weights [G][T][16^K] (and
+   tc [G][T][16^K][2]) and every after-state evaluated and updated in the tables of its own stage; it
+   refuses what that call refuses and a net g2048_ntuple_staged_weight_count refuses.  The workspaces are
+   those of the one-stage calls (g2048_ntuple_td_workspace_bytes and the others). */
+int g2048_ntuple_staged_value(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                              int64_t *value, int64_t n);
+int g2048_ntuple_staged_choose(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                               int64_t *q, uint8_t *legal, uint8_t *best, int64_t n);
+int g2048_ntuple_staged_td(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int8_t *boards, int8_t *after,
+                           uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
+                           const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
+int g2048_ntuple_staged_tc(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                           int8_t *after, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                           int32_t lr_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
+                           size_t workspace_bytes);
+int g2048_ntuple_staged_lambda(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                               int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
+                               int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
+                               const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes);
+int g2048_ntuple_staged_search(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
+                               int64_t n, int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal,
+                               uint8_t *best, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
