@@ -8,15 +8,16 @@
 // one 64-bit word; a table index is K nibbles of it, picked by wave-uniform shifts: the cells of
 // (tuple, symmetry) are one packed word of the kernel argument (scalar registers), the tuple length K
 // is a template parameter.  The gathers are one dword per lane at unrelated addresses; the updates are
-// no-return 32-bit atomic adds of the same shape.  A TD step is two launches: nt_td_eval_kernel only
-// reads the weights (choice, target, delta), nt_td_update_kernel only adds to them and steps the env,
-// and stream order between the two makes every read see the weights before the step's updates.
-// A TC step (temporal-coherence learning: a step size per weight out of 16 bytes of accumulators, E the
-// sum of the D a weight received and A the sum of their |D|) is three launches for the same reason:
-// nt_tc_weights_kernel between the two reads the records and adds each weight's share of D,
-// nt_tc_update_kernel adds to the records (64-bit atomics) and ends like nt_td_update_kernel.
-// The lambda step (g2048_ntuple_lambda, lambda = 2^-s) has the same launches with writing kernels of its
-// own (nt_lambda_*): they also add D >> k s to the after-state k moves older, kept per env in hist.
+// no-return 32-bit atomic adds of the same shape.  A learning step is up to three launches, and stream
+// order between them makes every read of a step see what it reads before the step's adds:
+// nt_td_eval_kernel only reads the weights (choice, target, D); nt_tc_weights_kernel, under rule TC only
+// (temporal-coherence learning: a step size per weight out of 16 bytes of accumulators, E the sum of the
+// D a weight received and A the sum of their |D|), reads the records and adds each weight's share of D;
+// nt_update_kernel adds D to the weights (TD) or to the records (TC, 64-bit atomics) and steps the env.
+// Two template switches beside K and S select what the two writing kernels hold: TC, the rule, and L,
+// whether there is a trace (g2048_ntuple_lambda, lambda = 2^-s, trace_len > 0): then D >> k s also goes to
+// the after-state k moves older, kept per env in hist.  Without the rule or the trace a kernel holds no
+// instruction for it, and an empty struct (one byte behind the others) in place of its arguments.
 // A net with stages (stage_map != 0) has G sets of tables, [G][T][16^K]: every board evaluated or updated
 // goes to the tuple rows of its own stage (nt_row of ntuple_net.hpp, a function of its largest nibble), in
 // kernels instantiated with S = true beside the one-stage ones.  nt_stage_kernel writes the stages of
@@ -187,27 +188,6 @@ __device__ __forceinline__ void nt_count_updates(long long *stats, bool updated)
     }
 }
 
-// TD step, the writing half: the update of the pending after-state, then the env step
-template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_td_update_kernel(NtArgs net, uint4 *__restrict__ boards,
-                                                           uint4 *__restrict__ after, uint8_t *__restrict__ pending,
-                                                           long long *__restrict__ run_score,
-                                                           const int32_t *__restrict__ ws_d,
-                                                           const uint8_t *__restrict__ ws_act, RngArgs rng, uint64_t t,
-                                                           long long *__restrict__ stats, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool valid = i < n;
-    bool updated = false;
-    if (valid) {
-        const uint32_t p = pending[i];
-        const int32_t D = ws_d[i];
-        updated = p != 0u;
-        if (updated && D != 0) nt_add<K, S>(net, nt_pack(after[i]), D);
-        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
-    }
-    nt_count_updates(stats, updated);
-}
-
 // add_i of the TC step: what a weight with the record (E, A) takes of D (include/g2048_ntuple.h)
 // Without a branch on A, so that both words of a record are always used and its gather stays one load.
 __device__ __forceinline__ int32_t nt_tc_share(long long E, unsigned long long A, int32_t D) {
@@ -220,22 +200,12 @@ __device__ __forceinline__ int32_t nt_tc_share(long long E, unsigned long long A
     return A == 0ull ? D : D < 0 ? -(int32_t)q : (int32_t)q;
 }
 
-// TC step, the launch between the two of the TD step: reads the accumulator records of the pending
-// after-state's 8 T weights (one 16-byte gather each, the 8 of a tuple issued together) and adds each
-// weight's share of D to it.  It writes W only; E and A are only read here and only added to in the
-// next launch, so every lane sees the records before the step's adds.
 typedef long long NtRecord __attribute__((ext_vector_type(2)));  // (E, A): one 16-byte load, not two of 8
 
+// TC, to W: the accumulator records of the 8 T weights of x are read (one 16-byte gather each, the 8 of a
+// tuple issued together) and each weight takes its share of D.  E and A are only read here.
 template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const NtRecord *__restrict__ tc,
-                                                            const uint4 *__restrict__ after,
-                                                            const uint8_t *__restrict__ pending,
-                                                            const int32_t *__restrict__ ws_d, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const int32_t D = ws_d[i];
-    if (pending[i] == 0u || D == 0) return;
-    const uint64_t x = nt_pack(after[i]);
+__device__ __forceinline__ void nt_tc_share_add(const NtArgs &net, const NtRecord *tc, uint64_t x, int32_t D) {
     const uint32_t row = nt_row<S>(net, x);
     for (int t = 0; t < net.T; t++) {
         const size_t base = (size_t)(row + t) << (4 * K);
@@ -254,46 +224,26 @@ __global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const Nt
     }
 }
 
-// TC step, the last launch: D to E and |D| to A of the same 8 T records, then the env step
+// TC, to the records: D to E and |D| to A of the same 8 T records (64-bit atomics)
 template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_tc_update_kernel(NtArgs net, unsigned long long *__restrict__ tc,
-                                                           uint4 *__restrict__ boards, uint4 *__restrict__ after,
-                                                           uint8_t *__restrict__ pending,
-                                                           long long *__restrict__ run_score,
-                                                           const int32_t *__restrict__ ws_d,
-                                                           const uint8_t *__restrict__ ws_act, RngArgs rng, uint64_t t,
-                                                           long long *__restrict__ stats, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool valid = i < n;
-    bool updated = false;
-    if (valid) {
-        const uint32_t p = pending[i];
-        const int32_t D = ws_d[i];
-        updated = p != 0u;
-        if (updated && D != 0) {
-            const uint64_t x = nt_pack(after[i]);
-            const unsigned long long dE = (unsigned long long)(long long)D, dA = D < 0 ? 0ull - dE : dE;
-            const uint32_t row = nt_row<S>(net, x);
-            for (int tt = 0; tt < net.T; tt++) {
-                unsigned long long *rec = tc + ((size_t)(row + tt) << (4 * K + 1));
+__device__ __forceinline__ void nt_tc_record_add(const NtArgs &net, unsigned long long *tc, uint64_t x, int32_t D) {
+    const unsigned long long dE = (unsigned long long)(long long)D, dA = D < 0 ? 0ull - dE : dE;
+    const uint32_t row = nt_row<S>(net, x);
+    for (int t = 0; t < net.T; t++) {
+        unsigned long long *rec = tc + ((size_t)(row + t) << (4 * K + 1));
 #pragma unroll
-                for (int g = 0; g < 8; g++) {
-                    const size_t k = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
-                    __hip_atomic_fetch_add(rec + k, dE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_fetch_add(rec + k + 1, dA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
+        for (int g = 0; g < 8; g++) {
+            const size_t k = (size_t)nt_index<K>(x, net.cells[8 * t + g]) << 1;
+            __hip_atomic_fetch_add(rec + k, dE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(rec + k + 1, dA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
     }
-    nt_count_updates(stats, updated);
 }
 
-// ---- the lambda step (g2048_ntuple_lambda): the D of after[i] also goes, shifted right by k s, to the
-// after-state k moves older of the same game, k = 1 .. hist_len[i] <= h, out of hist [h][n] boards.
-// The reading launch is nt_td_eval_kernel; the writing launches are the three below, one lane per env,
-// k the outer loop.  A lane loads its h rows of hist once, before any store, and only the step's last
-// launch moves them on, after its adds.
+// ---- the trace (g2048_ntuple_lambda, trace_len > 0): the D of after[i] also goes, shifted right by k s, to
+// the after-state k moves older of the same game, k = 1 .. hist_len[i] <= h, out of hist [h][n] boards.
+// A lane loads its h rows of hist once, before any store, and only the step's last launch moves them on,
+// after its adds.
 
 constexpr int kMaxTrace = G2048_NT_MAX_TRACE;
 
@@ -341,105 +291,90 @@ __device__ __forceinline__ void nt_trace_store(const NtTrace &tr, uint4 *hist, u
     hist_len[i] = (uint8_t)len;
 }
 
-// TD(lambda), the writing half: D_k to the 8 T weights of s_k, then the history and the env step
-template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_lambda_td_update_kernel(
-    NtArgs net, uint4 *__restrict__ boards, uint4 *__restrict__ after, uint4 *__restrict__ hist,
-    uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending, long long *__restrict__ run_score,
-    const int32_t *__restrict__ ws_d, const uint8_t *__restrict__ ws_act, int h, int s, RngArgs rng, uint64_t t,
-    long long *__restrict__ stats, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool valid = i < n;
-    bool updated = false;
-    if (valid) {
-        const uint32_t p = pending[i];
-        const int32_t D = ws_d[i];
-        const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
-        updated = p != 0u;
-        if (updated) {
+// f(s_k, D_k) for k = 0 .. tr.len with D_k != 0, k the outer loop, unrolled
+template <typename F>
+__device__ __forceinline__ void nt_for_trace(const NtTrace &tr, int32_t D, int s, F f) {
 #pragma unroll
-            for (int k = 0; k <= kMaxTrace; k++) {
-                const int32_t Dk = nt_decay(D, k * s);
-                if ((uint32_t)k <= tr.len && Dk != 0) nt_add<K, S>(net, tr.x[k], Dk);
-            }
-        }
-        nt_trace_store(tr, hist, hist_len, h, p, ws_act[i] != 0xFFu, n, i);
-        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
+    for (int k = 0; k <= kMaxTrace; k++) {
+        const int32_t Dk = nt_decay(D, k * s);
+        if ((uint32_t)k <= tr.len && Dk != 0) f(tr.x[k], Dk);
     }
-    nt_count_updates(stats, updated);
 }
 
-// TC(lambda), the launch between: per (k, tuple) the 8 records of s_k are gathered together and each
-// weight takes its share of D_k.  hist is only read here.
-template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_lambda_tc_weights_kernel(
-    NtArgs net, const NtRecord *__restrict__ tc, const uint4 *__restrict__ after, const uint4 *__restrict__ hist,
-    const uint8_t *__restrict__ hist_len, const uint8_t *__restrict__ pending, const int32_t *__restrict__ ws_d, int h,
-    int s, uint32_t n) {
+// The optional kernel arguments, last in the list: the `false` ones are empty and take what the `true`
+// ones take, so that a launch site is written once
+template <bool TC>
+struct NtTcArgs {
+    NtTcArgs(int64_t *) {}
+};
+template <>
+struct NtTcArgs<true> {
+    int64_t *tc;  // [G][T][16^K][2]
+};
+template <bool L>
+struct NtTraceArgs {
+    NtTraceArgs(int8_t *, uint8_t *, int, int) {}
+};
+template <>
+struct NtTraceArgs<true> {
+    int8_t *hist;
+    uint8_t *hist_len;
+    int h, s;
+};
+
+// The launch between the two others, rule TC only: each weight of the pending after-state (L: and of the
+// s_k of its trace) takes its share of D (D_k).  It writes W only; the records are only added to in the next
+// launch and hist only moves on there, so every lane sees both as they were before the step.
+template <int K, bool S, bool L>
+__global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const NtRecord *__restrict__ tc,
+                                                            const uint4 *__restrict__ after,
+                                                            const uint8_t *__restrict__ pending,
+                                                            const int32_t *__restrict__ ws_d, uint32_t n,
+                                                            NtTraceArgs<L> trace) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const int32_t D = ws_d[i];
     if (pending[i] == 0u || D == 0) return;
-    const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
-#pragma unroll
-    for (int k = 0; k <= kMaxTrace; k++) {
-        const int32_t Dk = nt_decay(D, k * s);
-        if ((uint32_t)k > tr.len || Dk == 0) continue;
-        const uint64_t x = tr.x[k];
-        const uint32_t row = nt_row<S>(net, x);
-        for (int t = 0; t < net.T; t++) {
-            const size_t base = (size_t)(row + t) << (4 * K);
-            uint32_t idx[8];
-            NtRecord r[8];
-#pragma unroll
-            for (int g = 0; g < 8; g++) {
-                idx[g] = nt_index<K>(x, net.cells[8 * t + g]);
-                r[g] = tc[base + idx[g]];
-            }
-#pragma unroll
-            for (int g = 0; g < 8; g++)
-                __hip_atomic_fetch_add((uint32_t *)net.w + base + idx[g],
-                                       (uint32_t)nt_tc_share(r[g].x, (unsigned long long)r[g].y, Dk), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        }
+    if constexpr (L) {
+        const NtTrace tr = nt_trace_load(after, (const uint4 *)trace.hist, trace.hist_len, trace.h, n, i);
+        nt_for_trace(tr, D, trace.s, [&](uint64_t x, int32_t Dk) __attribute__((always_inline)) {
+            nt_tc_share_add<K, S>(net, tc, x, Dk);
+        });
+    } else {
+        nt_tc_share_add<K, S>(net, tc, nt_pack(after[i]), D);
     }
 }
 
-// TC(lambda), the last launch: D_k to E and |D_k| to A of the records of s_k, then as the TD(lambda) one
-template <int K, bool S>
-__global__ __launch_bounds__(256) void nt_lambda_tc_update_kernel(
-    NtArgs net, unsigned long long *__restrict__ tc, uint4 *__restrict__ boards, uint4 *__restrict__ after,
-    uint4 *__restrict__ hist, uint8_t *__restrict__ hist_len, uint8_t *__restrict__ pending,
-    long long *__restrict__ run_score, const int32_t *__restrict__ ws_d, const uint8_t *__restrict__ ws_act, int h, int s,
-    RngArgs rng, uint64_t t, long long *__restrict__ stats, uint32_t n) {
+// A step's last launch: D (L: D_k) of the pending after-state (of s_k) to its 8 T weights, or under TC to
+// their records; then the history (L) and the env step
+template <int K, bool S, bool L, bool TC>
+__global__ __launch_bounds__(256) void nt_update_kernel(NtArgs net, uint4 *__restrict__ boards,
+                                                        uint4 *__restrict__ after, uint8_t *__restrict__ pending,
+                                                        long long *__restrict__ run_score,
+                                                        const int32_t *__restrict__ ws_d,
+                                                        const uint8_t *__restrict__ ws_act, RngArgs rng, uint64_t t,
+                                                        long long *__restrict__ stats, uint32_t n, NtTcArgs<TC> tc,
+                                                        NtTraceArgs<L> trace) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const bool valid = i < n;
     bool updated = false;
     if (valid) {
         const uint32_t p = pending[i];
         const int32_t D = ws_d[i];
-        const NtTrace tr = nt_trace_load(after, hist, hist_len, h, n, i);
         updated = p != 0u;
-        if (updated) {
-#pragma unroll
-            for (int k = 0; k <= kMaxTrace; k++) {
-                const int32_t Dk = nt_decay(D, k * s);
-                if ((uint32_t)k > tr.len || Dk == 0) continue;
-                const uint64_t x = tr.x[k];
-                const unsigned long long dE = (unsigned long long)(long long)Dk, dA = Dk < 0 ? 0ull - dE : dE;
-                const uint32_t row = nt_row<S>(net, x);
-                for (int tt = 0; tt < net.T; tt++) {
-                    unsigned long long *rec = tc + ((size_t)(row + tt) << (4 * K + 1));
-#pragma unroll
-                    for (int g = 0; g < 8; g++) {
-                        const size_t j = (size_t)nt_index<K>(x, net.cells[8 * tt + g]) << 1;
-                        __hip_atomic_fetch_add(rec + j, dE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_fetch_add(rec + j + 1, dA, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-            }
+        const auto add = [&](uint64_t x, int32_t Dk) __attribute__((always_inline)) {
+            if constexpr (TC)
+                nt_tc_record_add<K, S>(net, (unsigned long long *)tc.tc, x, Dk);
+            else
+                nt_add<K, S>(net, x, Dk);
+        };
+        if constexpr (L) {
+            const NtTrace tr = nt_trace_load(after, (const uint4 *)trace.hist, trace.hist_len, trace.h, n, i);
+            if (updated) nt_for_trace(tr, D, trace.s, add);
+            nt_trace_store(tr, (uint4 *)trace.hist, trace.hist_len, trace.h, p, ws_act[i] != 0xFFu, n, i);
+        } else if (updated && D != 0) {
+            add(nt_pack(after[i]), D);
         }
-        nt_trace_store(tr, hist, hist_len, h, p, ws_act[i] != 0xFFu, n, i);
         nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
     }
     nt_count_updates(stats, updated);
@@ -453,7 +388,7 @@ size_t td_workspace_bytes(int64_t n) { return align16((size_t)n * 4) + align16((
 extern "C" {
 
 // nt_call_<call>(stream, net, stage_map, ...): the body of g2048_ntuple_<call> (stage_map 0) and of its twin
-// g2048_ntuple_staged_<call>, both at the end of the file
+// g2048_ntuple_staged_<call>, both at the end of the file; the three learning calls share nt_call_step
 
 size_t g2048_ntuple_weight_count(const g2048_ntuple_net *net) {
     NtArgs a;
@@ -491,8 +426,7 @@ int g2048_ntuple_promote(g2048_stream_t stream, const g2048_ntuple_staged_net *s
 }
 
 static int nt_call_value(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, const int8_t *boards,
-                         int64_t *value,
-                       int64_t n) {
+                         int64_t *value, int64_t n) {
     NtArgs a;
     if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
     if (n == 0) return G2048_OK;
@@ -522,90 +456,17 @@ size_t g2048_ntuple_td_workspace_bytes(int64_t n) {
     return td_workspace_bytes(n < 1 ? 1 : n);
 }
 
-static int nt_call_td(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int8_t *boards, int8_t *after,
-                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
-                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes_in) {
-    NtArgs a;
-    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
-    if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
-    if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
-    if (n == 0) return G2048_OK;
-    if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
-        ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||
-        workspace_bytes_in < td_workspace_bytes(n))
-        return G2048_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    int32_t *ws_d = (int32_t *)workspace;
-    uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
-    const RngArgs r = rng_args(rng);
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(a, net->tuple_len,
-                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
-                                             (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
-                                             (uint32_t)n));
-        int s = launch_status();
-        if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(a, net->tuple_len,
-                          hipLaunchKernelGGL((nt_td_update_kernel<kK, kS>), grid, block, 0, st, a, (uint4 *)boards,
-                                             (uint4 *)after, pending, (long long *)run_score, (const int32_t *)ws_d,
-                                             (const uint8_t *)ws_act, r, (uint64_t)t, (long long *)stats, (uint32_t)n));
-        s = launch_status();
-        if (s != G2048_OK) return s;
-    }
-    return G2048_OK;
-}
-
 size_t g2048_ntuple_tc_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
-
-static int nt_call_tc(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc, int8_t *boards, int8_t *after,
-                    uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
-                    const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes_in) {
-    NtArgs a;
-    if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
-    if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
-    if (!philox_mode(rng) || !counter_dev_aligned(rng)) return G2048_EINVAL;
-    if (!tc || !aligned16(tc)) return G2048_EINVAL;
-    if (n == 0) return G2048_OK;
-    if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
-        ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||
-        workspace_bytes_in < td_workspace_bytes(n))
-        return G2048_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    int32_t *ws_d = (int32_t *)workspace;
-    uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
-    const RngArgs r = rng_args(rng);
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(a, net->tuple_len,
-                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
-                                             (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
-                                             (uint32_t)n));
-        int s = launch_status();
-        if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(a, net->tuple_len,
-                          hipLaunchKernelGGL((nt_tc_weights_kernel<kK, kS>), grid, block, 0, st, a, (const NtRecord *)tc,
-                                             (const uint4 *)after, (const uint8_t *)pending, (const int32_t *)ws_d,
-                                             (uint32_t)n));
-        s = launch_status();
-        if (s != G2048_OK) return s;
-        G2048_NT_DISPATCH(a, net->tuple_len,
-                          hipLaunchKernelGGL((nt_tc_update_kernel<kK, kS>), grid, block, 0, st, a, (unsigned long long *)tc,
-                                             (uint4 *)boards, (uint4 *)after, pending, (long long *)run_score,
-                                             (const int32_t *)ws_d, (const uint8_t *)ws_act, r, (uint64_t)t,
-                                             (long long *)stats, (uint32_t)n));
-        s = launch_status();
-        if (s != G2048_OK) return s;
-    }
-    return G2048_OK;
-}
-
 size_t g2048_ntuple_lambda_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
 
-static int nt_call_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc, int8_t *boards, int8_t *after,
-                        int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
-                        int32_t lr_shift, int32_t trace_len, int32_t lambda_shift, const g2048_rng *rng, int64_t *stats,
-                        void *workspace, size_t workspace_bytes_in) {
+// The three learning calls: `steps` steps of eval, weights (tc != null: rule TC) and update, the two
+// writing kernels with the trace where trace_len > 0.  g2048_ntuple_td comes with tc null, trace_len 0 and
+// lambda_shift 1; hist and hist_len are looked at only where there is a trace.
+static int nt_call_step(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc,
+                        int8_t *boards, int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending,
+                        int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len,
+                        int32_t lambda_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
+                        size_t workspace_bytes_in) {
     NtArgs a;
     if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
@@ -623,40 +484,41 @@ static int nt_call_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, ui
     int32_t *ws_d = (int32_t *)workspace;
     uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
     const RngArgs r = rng_args(rng);
-    const int h = trace_len, ls = lambda_shift;
+    const int K = net->tuple_len, h = trace_len, ls = lambda_shift;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(a, net->tuple_len,
+        G2048_NT_DISPATCH(a, K,
                           hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
                                              (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
                                              (uint32_t)n));
         int s = launch_status();
         if (s != G2048_OK) return s;
         if (tc) {
-            G2048_NT_DISPATCH(a, net->tuple_len,
-                              hipLaunchKernelGGL((nt_lambda_tc_weights_kernel<kK, kS>), grid, block, 0, st, a,
-                                                 (const NtRecord *)tc, (const uint4 *)after, (const uint4 *)hist,
-                                                 (const uint8_t *)hist_len, (const uint8_t *)pending,
-                                                 (const int32_t *)ws_d, h, ls, (uint32_t)n));
+            G2048_NT_DISPATCH_BOOL(h > 0, kL, G2048_NT_DISPATCH(a, K,
+                hipLaunchKernelGGL((nt_tc_weights_kernel<kK, kS, kL>), grid, block, 0, st, a, (const NtRecord *)tc,
+                                   (const uint4 *)after, (const uint8_t *)pending, (const int32_t *)ws_d, (uint32_t)n,
+                                   NtTraceArgs<kL>{hist, hist_len, h, ls})));
             s = launch_status();
             if (s != G2048_OK) return s;
-            G2048_NT_DISPATCH(a, net->tuple_len,
-                              hipLaunchKernelGGL((nt_lambda_tc_update_kernel<kK, kS>), grid, block, 0, st, a,
-                                                 (unsigned long long *)tc, (uint4 *)boards, (uint4 *)after, (uint4 *)hist,
-                                                 hist_len, pending, (long long *)run_score, (const int32_t *)ws_d,
-                                                 (const uint8_t *)ws_act, h, ls, r, (uint64_t)t, (long long *)stats,
-                                                 (uint32_t)n));
-        } else {
-            G2048_NT_DISPATCH(a, net->tuple_len,
-                              hipLaunchKernelGGL((nt_lambda_td_update_kernel<kK, kS>), grid, block, 0, st, a, (uint4 *)boards,
-                                                 (uint4 *)after, (uint4 *)hist, hist_len, pending, (long long *)run_score,
-                                                 (const int32_t *)ws_d, (const uint8_t *)ws_act, h, ls, r, (uint64_t)t,
-                                                 (long long *)stats, (uint32_t)n));
         }
+        G2048_NT_DISPATCH_BOOL(h > 0, kL, G2048_NT_DISPATCH_BOOL(tc != nullptr, kTC, G2048_NT_DISPATCH(a, K,
+            hipLaunchKernelGGL((nt_update_kernel<kK, kS, kL, kTC>), grid, block, 0, st, a, (uint4 *)boards, (uint4 *)after,
+                               pending, (long long *)run_score, (const int32_t *)ws_d, (const uint8_t *)ws_act, r,
+                               (uint64_t)t, (long long *)stats, (uint32_t)n, NtTcArgs<kTC>{tc},
+                               NtTraceArgs<kL>{hist, hist_len, h, ls}))));
         s = launch_status();
         if (s != G2048_OK) return s;
     }
     return G2048_OK;
+}
+
+// g2048_ntuple_tc has no TD form: it refuses a null tc, whatever n
+static int nt_call_tc(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc,
+                      int8_t *boards, int8_t *after, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
+                      int32_t lr_shift, const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
+    if (!tc) return G2048_EINVAL;
+    return nt_call_step(stream, net, stage_map, tc, boards, after, nullptr, nullptr, pending, run_score, n, steps,
+                        lr_shift, 0, 1, rng, stats, workspace, workspace_bytes);
 }
 
 // ---- the entry points: a one-stage call is its twin on a staged net with the map 0
@@ -683,14 +545,14 @@ int g2048_ntuple_staged_choose(g2048_stream_t stream, const g2048_ntuple_staged_
 int g2048_ntuple_td(g2048_stream_t stream, const g2048_ntuple_net *net, int8_t *boards, int8_t *after,
                     uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                     const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
-    return nt_call_td(stream, net, 0, boards, after, pending, run_score, n, steps, lr_shift, rng, stats, workspace,
-                      workspace_bytes);
+    return nt_call_step(stream, net, 0, nullptr, boards, after, nullptr, nullptr, pending, run_score, n, steps,
+                        lr_shift, 0, 1, rng, stats, workspace, workspace_bytes);
 }
 int g2048_ntuple_staged_td(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int8_t *boards, int8_t *after,
                            uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift,
                            const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
-    return nt_call_td(stream, NT_STAGED(net), boards, after, pending, run_score, n, steps, lr_shift, rng, stats,
-                      workspace, workspace_bytes);
+    return nt_call_step(stream, NT_STAGED(net), nullptr, boards, after, nullptr, nullptr, pending, run_score, n, steps,
+                        lr_shift, 0, 1, rng, stats, workspace, workspace_bytes);
 }
 
 int g2048_ntuple_tc(g2048_stream_t stream, const g2048_ntuple_net *net, int64_t *tc, int8_t *boards, int8_t *after,
@@ -711,15 +573,15 @@ int g2048_ntuple_lambda(g2048_stream_t stream, const g2048_ntuple_net *net, int6
                         int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score, int64_t n, int64_t steps,
                         int32_t lr_shift, int32_t trace_len, int32_t lambda_shift, const g2048_rng *rng, int64_t *stats,
                         void *workspace, size_t workspace_bytes) {
-    return nt_call_lambda(stream, net, 0, tc, boards, after, hist, hist_len, pending, run_score, n, steps, lr_shift,
-                          trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
+    return nt_call_step(stream, net, 0, tc, boards, after, hist, hist_len, pending, run_score, n, steps, lr_shift,
+                        trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
 }
 int g2048_ntuple_staged_lambda(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
                                int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
                                int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
                                const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
-    return nt_call_lambda(stream, NT_STAGED(net), tc, boards, after, hist, hist_len, pending, run_score, n, steps,
-                          lr_shift, trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
+    return nt_call_step(stream, NT_STAGED(net), tc, boards, after, hist, hist_len, pending, run_score, n, steps,
+                        lr_shift, trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -132,7 +132,16 @@ inline bool make_args(const g2048_ntuple_net *net, uint64_t stage_map, NtArgs &o
 }
 
 // fn<kK, kS>(args...) for the run-time tuple length K and kS = whether the net ARGS has stages (the inner
-// macro is variadic: CALL reaches it expanded, with commas of its own)
+// macros are variadic: CALL reaches them expanded, with commas of its own).  G2048_NT_DISPATCH_BOOL around
+// it adds a template switch NAME = COND of the caller's and nests: the whole stays one statement.
+#define G2048_NT_DISPATCH_BOOL(COND, NAME, ...)         \
+    if (COND) {                                         \
+        constexpr bool NAME = true;                     \
+        __VA_ARGS__;                                    \
+    } else {                                            \
+        constexpr bool NAME = false;                    \
+        __VA_ARGS__;                                    \
+    }
 #define G2048_NT_DISPATCH_K(K, ...)  \
     switch (K) {                     \
     case 1: { constexpr int kK = 1; __VA_ARGS__; } break; \
@@ -142,13 +151,7 @@ inline bool make_args(const g2048_ntuple_net *net, uint64_t stage_map, NtArgs &o
     case 5: { constexpr int kK = 5; __VA_ARGS__; } break; \
     default: { constexpr int kK = 6; __VA_ARGS__; } break; \
     }
-#define G2048_NT_DISPATCH(ARGS, K, CALL)   \
-    if ((ARGS).stage_map != 0) {           \
-        constexpr bool kS = true;          \
-        G2048_NT_DISPATCH_K(K, CALL)       \
-    } else {                               \
-        constexpr bool kS = false;         \
-        G2048_NT_DISPATCH_K(K, CALL)       \
-    }
+#define G2048_NT_DISPATCH(ARGS, K, CALL) \
+    G2048_NT_DISPATCH_BOOL((ARGS).stage_map != 0, kS, G2048_NT_DISPATCH_K(K, CALL))
 
 }  // namespace

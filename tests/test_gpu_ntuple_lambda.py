@@ -1,5 +1,5 @@
-"""TD(lambda) and TC(lambda) learning of the n-tuple network on the GPU (g2048_ntuple_lambda: the
-nt_lambda_* kernels of csrc/ntuple.hip; NTupleTrainer(trace_len=...); train-ntuple --trace), bit for bit
+"""TD(lambda) and TC(lambda) learning of the n-tuple network on the GPU (g2048_ntuple_lambda: nt_tc_weights_kernel
+and nt_update_kernel of csrc/ntuple.hip with the trace; NTupleTrainer(trace_len=...); train-ntuple --trace), bit for bit
 against the numpy reference of tests/ntuple_lambda_reference.py: every add is an integer fixed by reads
 that see the state before the step's adds, so the weights, the accumulators and the carried history
 after n envs learned in parallel must be the CPU's bytes whatever the order of the atomics.  The
@@ -27,6 +27,7 @@ import torch
 
 import ntuple_lambda_reference as LR
 import ntuple_reference as R
+import ntuple_stage_reference as SR
 import ntuple_tc_reference as C
 from conftest import PKG
 
@@ -157,6 +158,49 @@ def test_trace_zero_is_td_and_tc(dev, rule):
     torch.cuda.synchronize()
     assert_same(got, {k: v.cpu().numpy() for k, v in old.items()})
     assert (got["weights"] != w).any() and got["stats"][3] > 0
+
+
+@pytest.mark.parametrize("staged", [False, True], ids=["one-stage", "staged"])
+@pytest.mark.parametrize("rule", ["td", "tc"])
+def test_trace_zero_leaves_hist_alone(dev, rule, staged):
+    """h = 0 with hist int8 [4, n, 16] and hist_len uint8 [n] given all the same: the call runs the kernels
+    without a trace, both buffers keep their guard byte and everything else is g2048_ntuple_td / _tc's, byte for
+    byte.  n = 65 (one full wave and one lane), 20 steps, the first 65 envs of n300-random with the usual and
+    with SR.STAGES' tables."""
+    n, steps, guard = 65, 20, 0xA5
+    smap = SR.stage_map_of(SR.STAGES) if staged else 0
+    cells, w, boards, lr_shift, tc0 = SR.start(rule, "n300-random", "prefilled" if rule == "tc" else None, smap)
+
+    def state():
+        s = dict(weights=to_dev(w, dev), boards=to_dev(boards[:n], dev),
+                 after=torch.zeros(n, 16, dtype=torch.int8, device=dev),
+                 pending=torch.zeros(n, dtype=torch.uint8, device=dev),
+                 run_score=torch.zeros(n, dtype=torch.int64, device=dev),
+                 stats=torch.zeros(4, dtype=torch.int64, device=dev))
+        if rule == "tc":
+            s["tc"] = to_dev(tc0, dev)
+        return s, L().make_ntuple_net(cells, s["weights"], smap)
+
+    rng = L().make_rng(L().RNG_PHILOX, LR.SEED, 1)
+    ws = torch.full((L().ntuple_lambda_workspace_bytes(n),), GARBAGE, dtype=torch.uint8, device=dev)
+    hist = torch.full((4, n, 16), guard - 256, dtype=torch.int8, device=dev)
+    hist_len = torch.full((n,), guard, dtype=torch.uint8, device=dev)
+    new, net = state()
+    L().ntuple_lambda(net, new.get("tc"), new["boards"], new["after"], hist, hist_len, new["pending"],
+                      new["run_score"], steps, lr_shift, 0, 5, rng, new["stats"], ws)
+    old, net = state()
+    ws.fill_(GARBAGE)
+    if rule == "tc":
+        L().ntuple_tc(net, old["tc"], old["boards"], old["after"], old["pending"], old["run_score"], steps, lr_shift,
+                      rng, old["stats"], ws)
+    else:
+        L().ntuple_td(net, old["boards"], old["after"], old["pending"], old["run_score"], steps, lr_shift, rng,
+                      old["stats"], ws)
+    torch.cuda.synchronize()
+    assert bool((hist == guard - 256).all()) and bool((hist_len == guard).all())
+    new, old = ({k: v.cpu().numpy() for k, v in s.items()} for s in (new, old))
+    assert_same(new, old)
+    assert (new["weights"] != w).any() and new["stats"][3] > 0
 
 
 @pytest.mark.parametrize("rule,name,fill", [("td", "n64-random", None), ("tc", "n64-zero", "prefilled")])

@@ -1,5 +1,5 @@
 """Temporal-coherence learning of the n-tuple network on the GPU (g2048_ntuple_tc: nt_tc_weights_kernel,
-nt_tc_update_kernel of csrc/ntuple.hip; NTupleTrainer(rule="tc")), bit for bit against the numpy
+nt_update_kernel of csrc/ntuple.hip; NTupleTrainer(rule="tc")), bit for bit against the numpy
 reference of tests/ntuple_tc_reference.py: the weights' adds are integer quotients of accumulators read
 before the step's adds, and the accumulators' adds are integer sums, so the weights and the
 accumulators after n envs learned in parallel must be the CPU's bytes whatever the order of the atomics.
