@@ -87,8 +87,9 @@ __device__ __forceinline__ uint32_t fresh_stats(uint32_t p1, uint32_t v1, uint32
 // Step c (absolute Philox counter) takes word c & 1 of the stream-1 draw at counter c >> 1, so one
 // Philox draw serves two steps (and the reset that may end one of them).  The legal mask is
 // carried from the previous step (the action is always legal), and so are the kLine11 records of
-// the board's rows and columns, which hold the move in every direction, its points and the slid
-// lines' maximum: a step's only table reads are the records of the board it produces.  A board
+// the board's rows and columns, which hold the move in every direction (their first words; of the
+// second words, the sum and the maximum per orientation, which give the move's points and the slid
+// lines' maximum): a step's only table reads are the records of the board it produces.  A board
 // holding an exponent > 10 takes the SWAR compute path.  Workgroups are persistent over boards, so
 // large N keeps several waves per SIMD with one LDS table per CU.
 // kAddr = how a step forms its line addresses (rollout_step.hpp): the host takes the MFMA form where the
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(1024) void env_rollout_kernel(uint4 *__restrict__ b
         s.D = philox_draw(rng.seed, pair, env, 1u);
         s.ph = philox_start(rng.seed, pair + 1u, env, 1u);
         fresh_prep(s, s_row);
-        refill_lines<kAddr>(s, s_row, s.S >> 24, fa);
+        refill_lines<kAddr, true>(s, s_row, s.S >> 24, fa);
         // the record addresses of this board, from its own index in every trip of the board loop: wide,
         // per-lane pointers advanced one row (n elements) per step and no array base in an SGPR pair across
         // the loop; narrow, the five bases in SGPR pairs and three lane offsets advanced per step

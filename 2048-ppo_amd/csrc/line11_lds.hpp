@@ -21,12 +21,19 @@ static_assert(g2048::lut::line11_table_ok(g2048::lut::Line11Table()), "kLine11 f
 __device__ const g2048::lut::FreshTable kFresh __attribute__((aligned(16))) = g2048::lut::FreshTable();
 __device__ const g2048::lut::FreshLineTable kFreshLines __attribute__((aligned(16))) = g2048::lut::FreshLineTable();
 static_assert(g2048::lut::fresh_lines_ok(g2048::lut::FreshTable(), g2048::lut::FreshLineTable()), "kFreshLines against the kFresh boards");
+static_assert(g2048::lut::fresh_sums_ok(g2048::lut::FreshTable(), g2048::lut::FreshLineTable(), g2048::lut::Line11Table()),
+              "kFresh line sums against the kLine11 records of the kFresh boards");
 constexpr uint32_t kLineLdsBytes = g2048::lut::kFusedEntriesPadded * 8u;             // 117 760
 constexpr uint32_t kFreshBoardBase = kLineLdsBytes;                           // 15 KiB of boards
 constexpr uint32_t kFreshLineBase = kFreshBoardBase + g2048::lut::kFreshEntries * 16u;  // 15 KiB of line addresses
-constexpr uint32_t kFreshStatBase = kFreshLineBase + g2048::lut::kFreshEntries * 16u;   // 4 KiB of stats
-constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 4096u) / 4u;          // 152 576 B
+constexpr uint32_t kFreshStatBase = kFreshLineBase + g2048::lut::kFreshEntries * 16u;   // 8 KiB of {stats, line sums}
+constexpr uint32_t kFreshStatPieces = 8u;
+constexpr uint32_t kRolloutLdsWords = (kFreshStatBase + 1024u * kFreshStatPieces) / 4u;  // 156 672 B
 static_assert(kRolloutLdsWords * 4u <= 160u * 1024u, "the tables fit the 160 KiB of LDS");
+// mc_search_kernel plays out of kLine11 alone.  It keeps the allocation and the staging it was measured
+// with, which end behind the first half of the statistics pairs (it reads nothing past kLine11).
+constexpr uint32_t kSearchStatPieces = 4u;
+constexpr uint32_t kSearchLdsWords = (kFreshStatBase + 1024u * kSearchStatPieces) / 4u;  // 152 576 B
 // A kLine11 record sits at 8 idx (8 bytes, or the u16 at + 4) with every digit of the line <= 10.
 constexpr uint32_t kMaxLineDigit = g2048::lut::kLineBase - 1u;
 static_assert(8u * g2048::lut::line11_index(kMaxLineDigit, kMaxLineDigit, kMaxLineDigit, kMaxLineDigit) + 8u <= g2048::lut::kFusedEntries * 8u &&
@@ -167,6 +174,9 @@ __device__ __forceinline__ void line11_addrs_mfma(const uint4 &b, const i32x4 &f
 __device__ __forceinline__ uint2 lds_rec(const uint32_t *tab, uint32_t addr) {
     return *reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(tab) + addr);
 }
+__device__ __forceinline__ uint32_t lds_word(const uint32_t *tab, uint32_t addr) {  // a record's first word
+    return *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(tab) + addr);
+}
 __device__ __forceinline__ uint32_t lds_half(const uint32_t *tab, uint32_t addr) {
     return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(tab) + addr);
 }
@@ -262,14 +272,18 @@ __device__ __forceinline__ uint4 orient_rows(uint32_t e0, uint32_t e1, uint32_t 
 // flight before the single wait (one L2/MALL round trip per launch instead of one per batch).
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) void glb_void_t;
+// kStatPieces = how much of the statistics pairs the kernel's allocation holds (kFreshStatPieces: all of
+// them, kRolloutLdsWords; kSearchStatPieces: kSearchLdsWords).
+template <uint32_t kStatPieces = kFreshStatPieces>
 __device__ __forceinline__ void stage_row_table(uint32_t *s_row) {
     constexpr int kLinePieces = (int)(kLineLdsBytes / 1024u);                 // 115 pieces of 1 KiB
-    constexpr int kFreshPieces = (int)(g2048::lut::kFreshEntries * 16u / 1024u);     // + 15 boards + 15 line addresses + 4 stats
+    constexpr int kFreshPieces = (int)(g2048::lut::kFreshEntries * 16u / 1024u);     // + 15 boards + 15 line addresses + 8 stats
     static_assert(kLineLdsBytes % 1024u == 0u && g2048::lut::kFreshEntries * 16u % 1024u == 0u, "whole 1 KiB pieces");
     static_assert(sizeof(kLine11.v) == kLineLdsBytes && sizeof(kFresh.b) == kFreshPieces * 1024 &&
-                  sizeof(kFreshLines.a) == kFreshPieces * 1024 && sizeof(kFresh.st) == 4096, "table sizes");
-    constexpr int kAll = kLinePieces + 2 * kFreshPieces + 4;  // the LDS layout is the pieces in this order
-    static_assert(kAll * 1024 == (int)(kRolloutLdsWords * 4u), "the pieces fill the allocation");
+                  sizeof(kFreshLines.a) == kFreshPieces * 1024 && sizeof(kFresh.st) == 1024u * kFreshStatPieces &&
+                  kStatPieces <= kFreshStatPieces, "table sizes");
+    constexpr int kAll = kLinePieces + 2 * kFreshPieces + (int)kStatPieces;  // the LDS layout is the pieces in this order
+    static_assert(kAll * 1024 == (int)(kFreshStatBase + 1024u * kStatPieces), "the pieces fill the allocation");
     const char *src = reinterpret_cast<const char *>(kLine11.v);
     const char *src2 = reinterpret_cast<const char *>(kFresh.b);
     const char *src3 = reinterpret_cast<const char *>(kFreshLines.a);

@@ -66,8 +66,8 @@ __global__ __launch_bounds__(1024) void mc_search_kernel(const uint4 *__restrict
                                                          unsigned long long *__restrict__ move_sum,
                                                          uint8_t *__restrict__ legal_out, uint8_t *__restrict__ best_out,
                                                          uint32_t *__restrict__ arrived) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_row[kRolloutLdsWords];
-    stage_row_table(s_row);
+    __shared__ __attribute__((aligned(16))) uint32_t s_row[kSearchLdsWords];
+    stage_row_table<kSearchStatPieces>(s_row);
     const uint64_t ctr0 = rng_counter(rng);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t stride = gridDim.x * blockDim.x;  // total < 2^31, stride <= 2^18: L0 + stride fits

@@ -26,17 +26,30 @@ using namespace g2048;
 //    so its two steps index boards of exponents <= 9 and <= 10; every other step, and refill_lines,
 //    zeroes the board it takes addresses from in the lanes that hold an exponent > 10 (their reads are
 //    discarded: those lanes move on the SWAR path), and the spawn's pre-spawn lines are the post-spawn
-//    ones minus the spawned digit.
+//    ones minus the spawned digit.  (The kTraj step outside the fast pair moves a board whose maximum
+//    is exactly 10 on the SWAR path as well, for the points sum below; its addresses and its statistics
+//    still come from the table while the moved board stays <= 10.)
 constexpr uint32_t kFastPairMax = 8u;  // a pair runs with kSmall when every board's maximum is <= this
 static_assert(kFastPairMax + 1u + 1u <= kMaxLineDigit, "a fast pair (start <= 8) stays inside kLine11");
 //  - the kFreshLines addresses (<= kFreshLineAddrMax, checked entry by entry by fresh_lines_ok), which
 //    reset_reload reads in the lanes whose game ended
 static_assert(lut::kFreshLineAddrMax + 8u <= kLineLdsBytes, "fresh boards' line records inside kLine11");
-//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of line addresses and 4 B of
-//    statistics in fresh_prep (every lane, once per pair), 16 B of board at kFreshBoardBase + 16 i in
-//    reset_reload (the ending lanes)
+//  - a kFresh record i <= 959 (60 p1 + 4 k2 + 3, p1 <= 15, k2 <= 14): 16 B of line addresses and the 8 B
+//    pair of statistics and line sums in fresh_prep (every lane, once per pair), 16 B of board at
+//    kFreshBoardBase + 16 i in reset_reload (the ending lanes)
 static_assert(60u * 15u + 4u * 14u + 3u == lut::kFreshEntries - 1u, "kFresh index range");
-static_assert(kFreshStatBase + 4u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
+static_assert(kFreshStatBase + 8u * lut::kFreshEntries <= kRolloutLdsWords * 4u, "kFresh reads stay inside the allocation");
+
+// What the kTraj step takes from the carried line sums (RolloutLane hsR / hsC): bits 16..27 of the sum of
+// the four second words of an orientation are the move's points / 4 while that sum stays below 2^12 (the
+// low halves, line_entry, sum to at most 12 per nibble and never carry into bit 16).  A line of
+// exponents <= e scores at most two merges of 2^(e + 1) points.  The step reads the sums of a board whose
+// maximum is <= kFastPairMax + 1 in the fast pair's second step and <= kMaxLineDigit - 1 in the other
+// pair, whose lanes at kMaxLineDigit and above move on the SWAR path (sixteen 2^10 tiles would sum to
+// exactly 2^12).
+constexpr uint32_t line_points4_max(uint32_t e) { return 4u * 2u * ((2u << e) >> 2); }  // four lines
+static_assert(line_points4_max(kFastPairMax + 1u) < 4096u && line_points4_max(kMaxLineDigit - 1u) < 4096u &&
+              line_points4_max(kMaxLineDigit) == 4096u, "carried points sums stay inside their 12 bits");
 
 // Packed monotonicity statistics, one VGPR per board (step.hpp carry_pack): bits 0..3 pos (the first
 // row-major cell holding the maximum), 8..11 L, 12..15 R, 16..19 T, 20..23 B (board.hpp MonoStats),
@@ -65,7 +78,11 @@ struct RolloutLane {
     uint32_t S;       // kTraj: its packed monotonicity statistics (carry_pack); bits 24.. guard the table
     int empt_b;       // kTraj: its empty-cell count
     uint2 R[4], C[4]; // the kLine11 records of its rows and columns (valid while its maximum is <= 10;
-                      // a board above that moves on the SWAR path, which does not read them)
+                      // a board above that moves on the SWAR path, which does not read them).  kTraj: the
+                      // first words only; of the second words the step that loads them keeps ...
+    uint32_t hsR, hsC;  // kTraj: ... their sum over the rows and over the columns (bits 16..27: the points / 4
+                        // of a horizontal / vertical move of this board) ...
+    uint32_t hmR, hmC;  // kTraj: ... and their unsigned maximum (bits 28..31: the largest tile that move leaves)
     uint4 D;          // Philox draw of the current pair of steps: x / y = the two steps' words,
                       // z / w = the words of a reset inside the pair (at most one: a reset board
                       // cannot end again one move later; !kTraj: unused)
@@ -73,7 +90,8 @@ struct RolloutLane {
     // kTraj only:
     uint32_t fbo;     // the board a reset inside the current pair starts (D.z, D.w -> kFresh): its LDS
                       // byte address (kFreshBoardBase + 16 i), read only by the lanes whose game ends ...
-    uint32_t fst;     // ... its kFresh statistics word, as loaded: legal mask in bits 28..31, packed statistics below
+    uint2 fst;        // ... its kFresh pair, as loaded: x = legal mask in bits 28..31, packed statistics below;
+                      // y = its line sums (rowtable.hpp: hsR and hmR as it stands, hsC and hmC << 16)
     uint4 fla;        // ... and the LDS addresses of the kLine11 records of its rows and columns (8 x u16)
     // !kTraj only:
     uint32_t score;   // points so far
@@ -81,9 +99,9 @@ struct RolloutLane {
 };
 
 // the current pair's auto-reset board in kFresh (fresh_from_pair's board and fresh_stats' results):
-// its index, its statistics word and the addresses of the records of its eight lines (kFreshLines),
-// read once per pair right after the draw is known, long before a step can need them.  The board and
-// the eight records are read by reset_reload, in the lanes whose game ends and nowhere else.
+// its index, its pair of statistics and line sums and the addresses of the records of its eight lines
+// (kFreshLines), read once per pair right after the draw is known, long before a step can need them.
+// The board and the eight records are read by reset_reload, in the lanes whose game ends and nowhere else.
 __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__restrict__ tab) {
     const uint32_t a = s.D.z, bw = s.D.w;
     const uint64_t pb = (uint64_t)bw * 15u;  // one v_mad_u64_u32: k2 and the low word
@@ -93,28 +111,33 @@ __device__ __forceinline__ void fresh_prep(RolloutLane &s, const uint32_t *__res
     const char *t = reinterpret_cast<const char *>(tab);
     s.fbo = kFreshBoardBase + 16u * i;
     s.fla = *reinterpret_cast<const uint4 *>(t + kFreshLineBase + 16u * i);
-    // kept as loaded: splitting it here would stop the wave at this load once per pair, and nothing
-    // needs the two fields before a game ends (reset_reload's caller splits it, in the ending lanes)
-    s.fst = *reinterpret_cast<const uint32_t *>(t + kFreshStatBase + 4u * i);
+    // kept as loaded (one ds_read_b64): splitting it here would stop the wave at this load once per pair,
+    // and nothing needs its fields before a game ends (reset_reload's caller splits it, in the ending lanes)
+    s.fst = *reinterpret_cast<const uint2 *>(t + kFreshStatBase + 8u * i);
 }
 // The auto-reset of the lanes whose game ended (called under the divergent `if (over)`): the fresh
-// board and the records of its eight lines, loaded over the step's own b / R / C.  An exec-masked
-// load is a select that costs no VALU: the other lanes keep what the step's round trip loaded, and a
-// wave without an ending skips the block.  The empty asm keeps the address unpack inside the block
-// (the compiler would otherwise hoist the eight ALU operations into every step).
+// board and the first words of the records of its eight lines, loaded over the step's own b / R / C
+// (what a step needs of the second words comes from the kFresh pair, with no load here).  An
+// exec-masked load is a select that costs no VALU: the other lanes keep what the step's round trip
+// loaded, and a wave without an ending skips the block.  The empty asm keeps the address unpack inside
+// the block (the compiler would otherwise hoist the eight ALU operations into every step).
 __device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__restrict__ tab) {
     uint4 la = s.fla;
     asm volatile("" : "+v"(la.x), "+v"(la.y), "+v"(la.z), "+v"(la.w));
     // the board first: the next step stores it before it picks among the records
     s.b = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(tab) + s.fbo);
-    s.R[0] = lds_rec(tab, la.x & 0xFFFFu);
-    s.R[1] = lds_rec(tab, la.x >> 16);
-    s.R[2] = lds_rec(tab, la.y & 0xFFFFu);
-    s.R[3] = lds_rec(tab, la.y >> 16);
-    s.C[0] = lds_rec(tab, la.z & 0xFFFFu);
-    s.C[1] = lds_rec(tab, la.z >> 16);
-    s.C[2] = lds_rec(tab, la.w & 0xFFFFu);
-    s.C[3] = lds_rec(tab, la.w >> 16);
+    // (In index order.  The wait-count pass guards every first touch of these registers in the next step
+    // by a wait of its own, and issuing the loads in the reverse of that order makes one wait cover all
+    // eight: 506 -> 502 instructions and 13 -> 9 waits on the fast pair's path -- and 0.9 % slower in six
+    // rounds of six, profiles/r18a/ab_arms.log)
+    s.R[0].x = lds_word(tab, la.x & 0xFFFFu);
+    s.R[1].x = lds_word(tab, la.x >> 16);
+    s.R[2].x = lds_word(tab, la.y & 0xFFFFu);
+    s.R[3].x = lds_word(tab, la.y >> 16);
+    s.C[0].x = lds_word(tab, la.z & 0xFFFFu);
+    s.C[1].x = lds_word(tab, la.z >> 16);
+    s.C[2].x = lds_word(tab, la.w & 0xFFFFu);
+    s.C[3].x = lds_word(tab, la.w >> 16);
 }
 
 // How a step (and refill_lines) turns a board into the eight line addresses: line11_addrs (packed-u16
@@ -126,9 +149,9 @@ __device__ __forceinline__ void reset_reload(RolloutLane &s, const uint32_t *__r
 constexpr int kAddrValu = 0, kAddrMfma = 1;
 
 // the records of the current board's lines from the board itself (launch start; the steps keep them
-// up to date from then on).  A lane whose board holds an exponent > 10 (mx = its maximum) reads the
-// empty line's.
-template <int kAddr = kAddrValu>
+// up to date from then on), and (kTraj) the sums and maxima of their second words.  A lane whose board
+// holds an exponent > 10 (mx = its maximum) reads the empty line's.
+template <int kAddr = kAddrValu, bool kTraj = false>
 __device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__restrict__ tab, uint32_t mx, const i32x4 &fa = i32x4{}) {
     const uint4 ab = sel4(mx > kMaxLineDigit, make_uint4(0u, 0u, 0u, 0u), s.b);
     uint32_t ra[4], ca[4];
@@ -138,6 +161,12 @@ __device__ __forceinline__ void refill_lines(RolloutLane &s, const uint32_t *__r
     for (int i = 0; i < 4; i++) {
         s.R[i] = lds_rec(tab, ra[i]);
         s.C[i] = lds_rec(tab, ca[i]);
+    }
+    if constexpr (kTraj) {
+        s.hsR = s.R[0].y + s.R[1].y + s.R[2].y + s.R[3].y;
+        s.hsC = s.C[0].y + s.C[1].y + s.C[2].y + s.C[3].y;
+        s.hmR = max(max(s.R[0].y, s.R[1].y), max(s.R[2].y, s.R[3].y));
+        s.hmC = max(max(s.C[0].y, s.C[1].y), max(s.C[2].y, s.C[3].y));
     }
 }
 
@@ -239,8 +268,12 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const bool vert = a < 2u, rev = (a & 1u) != 0u;
     const uint32_t e0 = vert ? s.C[0].x : s.R[0].x, e1 = vert ? s.C[1].x : s.R[1].x;
     const uint32_t e2 = vert ? s.C[2].x : s.R[2].x, e3 = vert ? s.C[3].x : s.R[3].x;
-    const uint32_t h0 = vert ? s.C[0].y : s.R[0].y, h1 = vert ? s.C[1].y : s.R[1].y;
-    const uint32_t h2 = vert ? s.C[2].y : s.R[2].y, h3 = vert ? s.C[3].y : s.R[3].y;
+    // !kTraj: the second words of the chosen records, carried like the first
+    uint32_t h0 = 0u, h1 = 0u, h2 = 0u, h3 = 0u;
+    if constexpr (!kTraj) {
+        h0 = vert ? s.C[0].y : s.R[0].y, h1 = vert ? s.C[1].y : s.R[1].y;
+        h2 = vert ? s.C[2].y : s.R[2].y, h3 = vert ? s.C[3].y : s.R[3].y;
+    }
     const uint32_t mono_b = kTraj ? mono_value_packed(s.S) : 0u;
     // (two selects and an add: kPackEndAdd is wider than a 24-bit multiply-add takes.  The mask form --
     // v_bfe_i32 and v_and_or behind the select by vert, two VALU fewer per step -- measured 1.5 % slower
@@ -250,13 +283,24 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     const uint32_t psel = rev ? pbase + kPackEndAdd : pbase;
     uint4 moved = orient_rows(e0, e1, e2, e3, psel, vert);
     // merge points / 4 in bits 16..27 of each record's dword 1, the slid line's maximum in bits 28..31
-    uint32_t pts = (((h0 >> 16) & 0xFFFu) + ((h1 >> 16) & 0xFFFu) + ((h2 >> 16) & 0xFFFu) + ((h3 >> 16) & 0xFFFu)) << 2;
-    uint32_t Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(h0), as_u16x2(h1)),
-                                                                         __builtin_elementwise_max(as_u16x2(h2), as_u16x2(h3)))) >> 28;
+    uint32_t pts, Ma;
+    if constexpr (kTraj) {
+        // from what the previous step kept of the second words: the orientation's sum (its bits 16..27 are
+        // the points / 4: line_points4_max above) and its unsigned maximum (the maximum field is on top)
+        const uint32_t hs = vert ? s.hsC : s.hsR, hm = vert ? s.hmC : s.hmR;
+        pts = (hs >> 14) & 0x3FFCu;
+        Ma = hm >> 28;
+    } else {
+        pts = (((h0 >> 16) & 0xFFFu) + ((h1 >> 16) & 0xFFFu) + ((h2 >> 16) & 0xFFFu) + ((h3 >> 16) & 0xFFFu)) << 2;
+        Ma = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_elementwise_max(as_u16x2(h0), as_u16x2(h1)),
+                                                                    __builtin_elementwise_max(as_u16x2(h2), as_u16x2(h3)))) >> 28;
+    }
     // up to here the even step is the same in both pairs, and the compiler runs it in the pair loop's
     // header, ahead of the branch to either pair; the join the waits are about lies behind that branch
     if constexpr (kTraj && kSmall && !kOdd) __builtin_amdgcn_s_waitcnt(kWaitLds);
-    if (!kSmall && (kTraj ? s.S >> 24 : s.M) > kMaxLineDigit) {  // an exponent outside the table: the SWAR compute path
+    // an exponent outside the table: the SWAR compute path, exact for every board.  kTraj: from an exponent
+    // equal to kMaxLineDigit on, where the carried points sum can leave its field (line_points4_max)
+    if (!kSmall && (kTraj ? (s.S >> 24) >= kMaxLineDigit : s.M > kMaxLineDigit)) {
         uint32_t mx;
         moved = apply_move(s.b, a, pts, mx);
         Ma = board_max(moved);
@@ -378,8 +422,14 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
         tr.put_p(pts);
     }
     // line sums of the next board (bits 16..31 of a sum hold the points / maximum fields' sum, which no
-    // byte select below reads) and of the pre-spawn board
+    // byte select below reads: kTraj carries the sums for them, with the maxima of the same words, and
+    // nothing else of the second words reaches the next step) and of the pre-spawn board
     const uint32_t SR = R0.y + R1.y + R2.y + R3.y, SC = C0.y + C1.y + C2.y + C3.y;
+    if constexpr (kTraj) {
+        s.hsR = SR, s.hsC = SC;
+        s.hmR = max(max(R0.y, R1.y), max(R2.y, R3.y));  // v_max3_u32 and v_max_u32: no packed-operand hazard
+        s.hmC = max(max(C0.y, C1.y), max(C2.y, C3.y));
+    }
     const uint32_t SRp = SR - fq + fp, SCp = SC - gq + gp;
     // #lines that can move per direction in nibbles {UP, DOWN, LEFT, RIGHT} -> legal bits 0..3: a
     // nibble n in 0..4 gets bit 3 set by n + 7; the 24-bit product gathers bits 3, 7, 11, 15 at 12..15
@@ -387,8 +437,13 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
     s.legal = (__umul24((nl + 0x7777u) & 0x8888u, 0x249u) >> 12) & 15u;
     if (!kSmall && Ma > kMaxLineDigit) s.legal = legal_mask(moved);  // an exponent outside kLine11
     const bool over = s.legal == 0u;
-    s.R[0] = R0, s.R[1] = R1, s.R[2] = R2, s.R[3] = R3;
-    s.C[0] = C0, s.C[1] = C1, s.C[2] = C2, s.C[3] = C3;
+    if constexpr (kTraj) {
+        s.R[0].x = R0.x, s.R[1].x = R1.x, s.R[2].x = R2.x, s.R[3].x = R3.x;
+        s.C[0].x = C0.x, s.C[1].x = C1.x, s.C[2].x = C2.x, s.C[3].x = C3.x;
+    } else {
+        s.R[0] = R0, s.R[1] = R1, s.R[2] = R2, s.R[3] = R3;
+        s.C[0] = C0, s.C[1] = C1, s.C[2] = C2, s.C[3] = C3;
+    }
     if constexpr (kTraj) {
         // statistics before the spawn (the record's mono_a) and after it (carried to the next step): the
         // spawned tile changes the maximum / its first cell only when it reaches the maximum
@@ -420,10 +475,14 @@ __device__ __forceinline__ void rollout_step(RolloutLane &s, const uint32_t *__r
         // step's own lgkmcnt(0) (top of rollout_step) follows it there.
         if (over) {
             reset_reload(s, tab);
-            uint32_t st = s.fst;
-            asm volatile("" : "+v"(st));  // the split stays inside the block, like reset_reload's unpack
+            uint32_t st = s.fst.x, hw = s.fst.y;
+            asm volatile("" : "+v"(st), "+v"(hw));  // the split stays inside the block, like reset_reload's unpack
             s.legal = st >> 28;
             s.S = st & 0x0FFFFFFFu;
+            // the fresh board's line sums (rowtable.hpp FreshTable): the rows' fields stand where a sum
+            // and a maximum have theirs, the columns' 16 bits below
+            s.hsR = hw, s.hmR = hw;
+            s.hsC = hw << 16, s.hmC = hw << 16;
             fl = FLAG_DONE | FLAG_RESET | s.legal;
             s.empt_b = 14;
         }
