@@ -22,6 +22,11 @@
 // goes to the tuple rows of its own stage (nt_row of ntuple_net.hpp, a function of its largest nibble), in
 // kernels instantiated with S = true beside the one-stage ones.  nt_stage_kernel writes the stages of
 // boards, nt_promote_kernel adds one stage's tables to another's (g2048_ntuple_promote).
+// The carousel (g2048_ntuple_staged_carousel) is a third switch, C, on the reading kernel and on the last
+// one: a finished game restarts from a board with which some game entered a stage, out of a pool of one
+// slot per (stage, env).  The reading kernel picks every env's donor slot and start stage and leaves them in
+// the workspace; the last launch records the boards that enter a stage and applies the restart to the games
+// that end, so every read of the pool sees it as it was before the step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -125,13 +130,60 @@ __global__ __launch_bounds__(256) void nt_promote_kernel(const uint4 *__restrict
     }
 }
 
-// TD step, the reading half: the greedy action of the board and the D of the pending after-state
-template <int K, bool S>
+// The carousel's kernel arguments (Carousel of include/g2048_ntuple.h), last in the list of the two kernels
+// that take them; the `false` form is empty, as NtTcArgs / NtTraceArgs below
+template <bool C>
+struct NtCarArgs;
+template <>
+struct NtCarArgs<true> {
+    uint4 *pool;                  // [G][n]
+    uint8_t *valid;               // [n][16]
+    uint8_t *next, *origin;       // [n]
+    uint8_t *ws_stage;            // [n]: the start stage the reading kernel chose, 0: the reset
+    uint4 *ws_board;              // [n]: the donor board, written where ws_stage != 0
+    uint64_t ct;                  // rng->counter + t
+    const uint64_t *counter_dev;  // nullable
+};
+template <>
+struct NtCarArgs<false> {
+    NtCarArgs(const NtCarArgs<true> &) {}
+};
+
+// bit k of the result: byte k of w is not 0
+__device__ __forceinline__ uint32_t nt_nonzero_bytes(uint32_t w) {
+    return ((w & 0xFFu) != 0u ? 1u : 0u) | ((w & 0xFF00u) != 0u ? 2u : 0u) | ((w & 0xFF0000u) != 0u ? 4u : 0u) |
+           ((w & 0xFF000000u) != 0u ? 8u : 0u);
+}
+
+// Step 3c's choice, in the reading kernel: the donor slot j = (i + c + t) mod n, the sum modulo 2^64, and the
+// first stage at or after next[i] that the slot holds; k = 0, and a slot without such a stage, is the reset.
+// One 16-byte load brings the 16 flags of the slot.  The donor board is loaded only in the lanes that found a
+// stage, not unconditionally from row max(g, 1): that row does not exist in the pool of a one-stage net, and
+// the lanes at k = 0 (one in G) and those on an empty slot then move no board at all.  The branch costs one
+// test per wave; the lanes behind it issue one 16-byte load and one 16-byte store.
+__device__ __forceinline__ void nt_car_choose(const NtArgs &net, const NtCarArgs<true> &car, uint32_t n, uint32_t i) {
+    const uint64_t s = car.ct + (car.counter_dev ? *car.counter_dev : 0ull);
+    const uint32_t j = (uint32_t)((s + (uint64_t)i) % (uint64_t)n);
+    const uint32_t G = (uint32_t)net.G;
+    uint32_t k = car.next[i];
+    k = k < G ? k : 0u;
+    const uint4 f = reinterpret_cast<const uint4 *>(car.valid)[j];
+    uint32_t m = nt_nonzero_bytes(f.x) | (nt_nonzero_bytes(f.y) << 4) | (nt_nonzero_bytes(f.z) << 8) |
+                 (nt_nonzero_bytes(f.w) << 12);
+    m &= ((1u << G) - 1u) & ~((1u << k) - 1u) & ~1u;  // stages max(k, 1) .. G - 1
+    const uint32_t g = (k != 0u && m != 0u) ? (uint32_t)__builtin_ctz(m) : 0u;
+    car.ws_stage[i] = (uint8_t)g;
+    if (g != 0u) car.ws_board[i] = car.pool[(size_t)g * n + j];
+}
+
+// TD step, the reading half: the greedy action of the board and the D of the pending after-state (C: and the
+// carousel's choice for a game that ends in this step)
+template <int K, bool S, bool C>
 __global__ __launch_bounds__(256) void nt_td_eval_kernel(NtArgs net, const uint4 *__restrict__ boards,
                                                          const uint4 *__restrict__ after,
                                                          const uint8_t *__restrict__ pending, int lr_shift,
                                                          int32_t *__restrict__ ws_d, uint8_t *__restrict__ ws_act,
-                                                         uint32_t n) {
+                                                         uint32_t n, NtCarArgs<C> car) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const NtChoice c = nt_choose<K, S>(net, boards[i]);
@@ -147,31 +199,60 @@ __global__ __launch_bounds__(256) void nt_td_eval_kernel(NtArgs net, const uint4
     }
     ws_d[i] = (int32_t)D;
     ws_act[i] = (uint8_t)c.best;
+    if constexpr (C) nt_car_choose(net, car, n, i);
 }
 
 // The end of a step's last launch, the same for both learners: g2048_env_step of env i with the greedy
 // action and auto-reset at counter c + t, the running score, the finished game's statistics, and the
-// carried state (after, pending)
-__device__ __forceinline__ void nt_step_env(uint4 *boards, uint4 *after, uint8_t *pending, long long *run_score,
-                                            const uint8_t *ws_act, RngArgs rng, uint64_t t, long long *stats,
-                                            uint32_t i) {
+// carried state (after, pending).  C, the carousel: a board that enters a stage goes into the env's own pool
+// slot of that stage (a 16-byte store and a flag byte, in those lanes only), and a game that ends is
+// accounted by its origin and restarts from what the reading kernel chose.
+template <bool C>
+__device__ __forceinline__ void nt_step_env(const NtArgs &net, uint4 *boards, uint4 *after, uint8_t *pending,
+                                            long long *run_score, const uint8_t *ws_act, RngArgs rng, uint64_t t,
+                                            long long *stats, uint32_t n, uint32_t i, const NtCarArgs<C> &car) {
     const uint32_t act = ws_act[i];
     const bool has_move = act != 0xFFu;
     const uint32_t a = has_move ? act : 0u;
     uint4 b = boards[i];
+    [[maybe_unused]] const uint4 before = b;
     uint32_t pts, mx;
     const uint4 moved = apply_move(b, a, pts, mx);
     const StepResult res = step_board<G2048_RNG_PHILOX>(b, true, a, nullptr, rng, (int64_t)i, rng_counter(rng) + t,
                                                         G2048_OPT_AUTO_RESET);
     long long rs = run_score[i] + (long long)res.pts;
     const bool done = (res.fl & FLAG_DONE) != 0u;
+    if constexpr (C) {
+        const uint32_t g1 = nt_stage(net.stage_map, nt_pack(b));
+        if (!done && g1 != nt_stage(net.stage_map, nt_pack(before))) {  // the stage only grows inside a game: g1 >= 1
+            car.pool[(size_t)g1 * n + i] = b;
+            car.valid[16u * (size_t)i + g1] = (uint8_t)1;
+            if (stats) __hip_atomic_fetch_add(stats + 6, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     if (done) {
+        bool full = true;  // a game from the ordinary reset
+        if constexpr (C) full = car.origin[i] == (uint8_t)0;
         if (stats) {
-            __hip_atomic_fetch_add(stats + 0, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(stats + 1, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(stats + 2, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (full) {
+                __hip_atomic_fetch_add(stats + 0, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(stats + 1, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_max(stats + 2, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                __hip_atomic_fetch_add(stats + 4, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(stats + 5, rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         rs = 0;
+        if constexpr (C) {
+            const uint32_t g = car.ws_stage[i];
+            if (g != 0u) {
+                b = car.ws_board[i];
+                if (stats) __hip_atomic_fetch_add(stats + 7, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            car.origin[i] = (uint8_t)g;
+            car.next[i] = (uint8_t)(g + 1u == (uint32_t)net.G ? 0u : g + 1u);
+        }
     }
     run_score[i] = rs;
     boards[i] = b;
@@ -346,15 +427,15 @@ __global__ __launch_bounds__(256) void nt_tc_weights_kernel(NtArgs net, const Nt
 }
 
 // A step's last launch: D (L: D_k) of the pending after-state (of s_k) to its 8 T weights, or under TC to
-// their records; then the history (L) and the env step
-template <int K, bool S, bool L, bool TC>
+// their records; then the history (L) and the env step (C: with the carousel's snapshot and restart)
+template <int K, bool S, bool L, bool TC, bool C>
 __global__ __launch_bounds__(256) void nt_update_kernel(NtArgs net, uint4 *__restrict__ boards,
                                                         uint4 *__restrict__ after, uint8_t *__restrict__ pending,
                                                         long long *__restrict__ run_score,
                                                         const int32_t *__restrict__ ws_d,
                                                         const uint8_t *__restrict__ ws_act, RngArgs rng, uint64_t t,
                                                         long long *__restrict__ stats, uint32_t n, NtTcArgs<TC> tc,
-                                                        NtTraceArgs<L> trace) {
+                                                        NtTraceArgs<L> trace, NtCarArgs<C> car) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const bool valid = i < n;
     bool updated = false;
@@ -375,13 +456,15 @@ __global__ __launch_bounds__(256) void nt_update_kernel(NtArgs net, uint4 *__res
         } else if (updated && D != 0) {
             add(nt_pack(after[i]), D);
         }
-        nt_step_env(boards, after, pending, run_score, ws_act, rng, t, stats, i);
+        nt_step_env<C>(net, boards, after, pending, run_score, ws_act, rng, t, stats, n, i, car);
     }
     nt_count_updates(stats, updated);
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 size_t td_workspace_bytes(int64_t n) { return align16((size_t)n * 4) + align16((size_t)n); }
+// behind the TD step's workspace: the chosen start stage, a byte, and the donor board of every env
+size_t car_workspace_bytes(int64_t n) { return td_workspace_bytes(n) + align16((size_t)n) + (size_t)n * 16; }
 
 }  // namespace
 
@@ -458,15 +541,21 @@ size_t g2048_ntuple_td_workspace_bytes(int64_t n) {
 
 size_t g2048_ntuple_tc_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
 size_t g2048_ntuple_lambda_workspace_bytes(int64_t n) { return g2048_ntuple_td_workspace_bytes(n); }
+size_t g2048_ntuple_carousel_workspace_bytes(int64_t n) {
+    if (n < 0 || n >= (int64_t(1) << 28)) return 0;
+    return car_workspace_bytes(n < 1 ? 1 : n);
+}
 
 // The three learning calls: `steps` steps of eval, weights (tc != null: rule TC) and update, the two
 // writing kernels with the trace where trace_len > 0.  g2048_ntuple_td comes with tc null, trace_len 0 and
-// lambda_shift 1; hist and hist_len are looked at only where there is a trace.
+// lambda_shift 1; hist and hist_len are looked at only where there is a trace.  carousel: the call is
+// g2048_ntuple_staged_carousel, car is required and the two kernels that take it run in their S = true form
+// whatever the map (with the map 0 that form computes what S = false computes).
 static int nt_call_step(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, int64_t *tc,
                         int8_t *boards, int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending,
                         int64_t *run_score, int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len,
                         int32_t lambda_shift, const g2048_rng *rng, int64_t *stats, void *workspace,
-                        size_t workspace_bytes_in) {
+                        size_t workspace_bytes_in, bool carousel = false, const g2048_ntuple_carousel *car = nullptr) {
     NtArgs a;
     if (!make_args(net, stage_map, a) || n < 0 || n >= (int64_t(1) << 28)) return G2048_EINVAL;
     if (steps < 1 || lr_shift < 1 || lr_shift > 30) return G2048_EINVAL;
@@ -477,20 +566,30 @@ static int nt_call_step(g2048_stream_t stream, const g2048_ntuple_net *net, uint
     if (n == 0) return G2048_OK;
     if (!boards || !aligned16(boards) || !after || !aligned16(after) || !pending || !run_score ||
         ((uintptr_t)run_score & 7u) || ((uintptr_t)stats & 7u) || !workspace || !aligned16(workspace) ||
-        workspace_bytes_in < td_workspace_bytes(n))
+        workspace_bytes_in < (carousel ? car_workspace_bytes(n) : td_workspace_bytes(n)))
         return G2048_EINVAL;
     if (trace_len > 0 && (!hist || !aligned16(hist) || !hist_len)) return G2048_EINVAL;
+    if (carousel && (!car || !car->pool || !aligned16(car->pool) || !car->valid || !aligned16(car->valid) || !car->next ||
+                     !car->origin))
+        return G2048_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int32_t *ws_d = (int32_t *)workspace;
     uint8_t *ws_act = (uint8_t *)workspace + align16((size_t)n * 4);
+    NtCarArgs<true> ca{};
+    if (carousel) {
+        uint8_t *ws_stage = (uint8_t *)workspace + td_workspace_bytes(n);
+        ca = NtCarArgs<true>{(uint4 *)car->pool, car->valid, car->next, car->origin, ws_stage,
+                             (uint4 *)(ws_stage + align16((size_t)n)), 0, rng->counter_dev};
+    }
     const RngArgs r = rng_args(rng);
     const int K = net->tuple_len, h = trace_len, ls = lambda_shift;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int64_t t = 0; t < steps; t++) {
-        G2048_NT_DISPATCH(a, K,
-                          hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS>), grid, block, 0, st, a, (const uint4 *)boards,
-                                             (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act,
-                                             (uint32_t)n));
+        ca.ct = rng->counter + (uint64_t)t;
+        G2048_NT_DISPATCH_BOOL(carousel, kC, G2048_NT_DISPATCH(a, K,
+            hipLaunchKernelGGL((nt_td_eval_kernel<kK, kS || kC, kC>), grid, block, 0, st, a, (const uint4 *)boards,
+                               (const uint4 *)after, (const uint8_t *)pending, (int)lr_shift, ws_d, ws_act, (uint32_t)n,
+                               NtCarArgs<kC>(ca))));
         int s = launch_status();
         if (s != G2048_OK) return s;
         if (tc) {
@@ -501,11 +600,12 @@ static int nt_call_step(g2048_stream_t stream, const g2048_ntuple_net *net, uint
             s = launch_status();
             if (s != G2048_OK) return s;
         }
-        G2048_NT_DISPATCH_BOOL(h > 0, kL, G2048_NT_DISPATCH_BOOL(tc != nullptr, kTC, G2048_NT_DISPATCH(a, K,
-            hipLaunchKernelGGL((nt_update_kernel<kK, kS, kL, kTC>), grid, block, 0, st, a, (uint4 *)boards, (uint4 *)after,
-                               pending, (long long *)run_score, (const int32_t *)ws_d, (const uint8_t *)ws_act, r,
-                               (uint64_t)t, (long long *)stats, (uint32_t)n, NtTcArgs<kTC>{tc},
-                               NtTraceArgs<kL>{hist, hist_len, h, ls}))));
+        G2048_NT_DISPATCH_BOOL(carousel, kC, G2048_NT_DISPATCH_BOOL(h > 0, kL, G2048_NT_DISPATCH_BOOL(tc != nullptr, kTC,
+            G2048_NT_DISPATCH(a, K,
+                hipLaunchKernelGGL((nt_update_kernel<kK, kS || kC, kL, kTC, kC>), grid, block, 0, st, a, (uint4 *)boards,
+                                   (uint4 *)after, pending, (long long *)run_score, (const int32_t *)ws_d,
+                                   (const uint8_t *)ws_act, r, (uint64_t)t, (long long *)stats, (uint32_t)n,
+                                   NtTcArgs<kTC>{tc}, NtTraceArgs<kL>{hist, hist_len, h, ls}, NtCarArgs<kC>(ca))))));
         s = launch_status();
         if (s != G2048_OK) return s;
     }
@@ -582,6 +682,15 @@ int g2048_ntuple_staged_lambda(g2048_stream_t stream, const g2048_ntuple_staged_
                                const g2048_rng *rng, int64_t *stats, void *workspace, size_t workspace_bytes) {
     return nt_call_step(stream, NT_STAGED(net), tc, boards, after, hist, hist_len, pending, run_score, n, steps,
                         lr_shift, trace_len, lambda_shift, rng, stats, workspace, workspace_bytes);
+}
+
+int g2048_ntuple_staged_carousel(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                                 int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
+                                 int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
+                                 const g2048_rng *rng, const g2048_ntuple_carousel *car, int64_t *stats, void *workspace,
+                                 size_t workspace_bytes) {
+    return nt_call_step(stream, NT_STAGED(net), tc, boards, after, hist, hist_len, pending, run_score, n, steps,
+                        lr_shift, trace_len, lambda_shift, rng, stats, workspace, workspace_bytes, true, car);
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@ _STRUCT_NAMES = {
     "g2048_reward_cfg": "RewardCfg",
     "g2048_ntuple_net": "NtNet",
     "g2048_ntuple_staged_net": "NtStagedNet",
+    "g2048_ntuple_carousel": "NtCarousel",
     "g2048_dropout": "Dropout",
     "g2048_policy_rollout_args": "PolicyRolloutArgs",
     "g2048_colsum_job": "ColsumJob",
@@ -482,6 +483,48 @@ def ntuple_lambda(net, tc, boards, after, hist, hist_len, pending, run_score, st
           _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), trace_len, int(lambda_shift),
           ctypes.byref(rng), _dev(stats, torch.int64, "stats"), _dev(workspace, torch.uint8, "workspace"),
           workspace.numel())
+
+
+def ntuple_carousel_workspace_bytes(n: int) -> int:
+    """0 for an n g2048_ntuple_staged_carousel would refuse."""
+    return int(load().g2048_ntuple_carousel_workspace_bytes(int(n)))
+
+
+def ntuple_carousel(net, tc, boards, after, hist, hist_len, pending, run_score, steps: int, lr_shift: int,
+                    trace_len: int, lambda_shift: int, rng: Rng, pool, valid, next_stage, origin, stats=None,
+                    workspace=None):
+    """`steps` carousel steps of the n envs on a net with stages (g2048_ntuple_staged_carousel): ntuple_lambda's
+    arguments and the carried carousel state pool int8 [G, n, 16], valid uint8 [n, 16], next_stage / origin
+    uint8 [n]; stats int64 [8] accumulated (optional); workspace: a uint8 device tensor of
+    ntuple_carousel_workspace_bytes(n) bytes."""
+    n, trace_len = boards.shape[0], int(trace_len)
+    snet = _staged(net)
+    count = _ntuple_weight_count(net)
+    if tc is not None:
+        if tc.dtype != torch.int64 or tc.numel() != 2 * count or tc.device != boards.device:  # two int64 per weight
+            raise G2048Error(f"ntuple_carousel: tc must be int64 with {2 * count} elements on {boards.device}, got "
+                             f"{(tc.dtype, tc.numel(), tc.device)}")
+    if trace_len > 0 and (hist is None or hist_len is None):
+        raise G2048Error(f"ntuple_carousel: trace_len {trace_len} needs hist and hist_len")
+    if any(t is None for t in (pool, valid, next_stage, origin)):
+        raise G2048Error("ntuple_carousel: pool, valid, next_stage and origin are required")
+    G = 1 + ((int(snet.stage_map) >> 60) & 15)
+    for t, nm, k in ((after, "after", 16 * n), (hist, "hist", 16 * n * max(trace_len, 0)), (hist_len, "hist_len", n),
+                     (pending, "pending", n), (run_score, "run_score", n), (stats, "stats", 8),
+                     (pool, "pool", 16 * n * G), (valid, "valid", 16 * n), (next_stage, "next_stage", n),
+                     (origin, "origin", n)):
+        if t is not None and t.numel() < k:
+            raise G2048Error(f"ntuple_carousel: {nm} holds {t.numel()} elements, needs {k}")
+    if workspace is None:
+        raise G2048Error("ntuple_carousel: a workspace of ntuple_carousel_workspace_bytes(n) bytes is required")
+    car = NtCarousel(_dev(pool, torch.int8, "pool"), _dev(valid, torch.uint8, "valid"),
+                     _dev(next_stage, torch.uint8, "next_stage"), _dev(origin, torch.uint8, "origin"))
+    _call("g2048_ntuple_staged_carousel", _stream(boards), ctypes.byref(snet), _dev(tc, torch.int64, "tc"),
+          _dev(boards, torch.int8, "boards"), _dev(after, torch.int8, "after"), _dev(hist, torch.int8, "hist"),
+          _dev(hist_len, torch.uint8, "hist_len"), _dev(pending, torch.uint8, "pending"),
+          _dev(run_score, torch.int64, "run_score"), n, int(steps), int(lr_shift), trace_len, int(lambda_shift),
+          ctypes.byref(rng), ctypes.byref(car), _dev(stats, torch.int64, "stats"),
+          _dev(workspace, torch.uint8, "workspace"), workspace.numel())
 
 
 def preview_points(boards, points4):

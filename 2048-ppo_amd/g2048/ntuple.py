@@ -152,18 +152,27 @@ class NTupleTrainer:
     boards is in and promotes g - 1 -> g for every g in promoted_upto + 1 .. g*, in ascending order.  So every
     stage is promoted once, from the stage below it, the first time a cut sees a board at or above it;
     what the stage learned before that cut is kept, since promotion adds.  The accumulators of rule "tc"
-    are not promoted.  0: never, exactly the calls above."""
+    are not promoted.  0: never, exactly the calls above.
+    carousel (a net with stages only): every env remembers the board with which its game entered each stage
+    (self.pool int8 [G, envs, 16], self.valid uint8 [envs, 16]) and a finished game restarts from such a board
+    of another env's slot, going round the stages in turn (self.next_stage, self.origin uint8 [envs]):
+    g2048_ntuple_staged_carousel for every rule and trace.  train() then also returns restart_games and
+    restart_points (finished games that started from a snapshot, and their points since), recorded (snapshots
+    taken) and restarts; games / mean_score / max_score stay those of full games from the ordinary reset.  The
+    pool belongs to the trainer, like the accumulators.  False: exactly the calls above."""
 
     RULES = ("td", "tc")
 
     def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td",
-                 trace_len: int = 0, lambda_shift: int = 1, promote_every: int = 0):
+                 trace_len: int = 0, lambda_shift: int = 1, promote_every: int = 0, carousel: bool = False):
         envs, lr_shift, trace_len, lambda_shift = int(envs), int(lr_shift), int(trace_len), int(lambda_shift)
         promote_every = int(promote_every)
         if promote_every < 0:
             raise ValueError(f"promote_every must not be negative, got {promote_every}")
         if promote_every > 0 and not net.stages:
             raise ValueError("promote_every needs a net with stages")
+        if carousel and not net.stages:
+            raise ValueError("carousel needs a net with stages")
         if not 1 <= envs <= MAX_ENVS:
             raise ValueError(f"envs must be in [1, {MAX_ENVS}], got {envs}")
         if not 1 <= lr_shift <= 30:
@@ -177,6 +186,8 @@ class NTupleTrainer:
         self.net, self.envs, self.lr_shift, self.seed, self.rule = net, envs, lr_shift, int(seed), rule
         self.trace_len, self.lambda_shift = trace_len, lambda_shift
         self.promote_every, self.promoted_upto = promote_every, 0
+        self.carousel = bool(carousel)
+        self.pool = self.valid = self.next_stage = self.origin = None
         self.counter = 0
         self.boards = None
         self.tc = None
@@ -188,7 +199,7 @@ class NTupleTrainer:
         self.after = torch.zeros(n, 16, dtype=torch.int8, device=d)
         self.pending = torch.zeros(n, dtype=torch.uint8, device=d)
         self.run_score = torch.zeros(n, dtype=torch.int64, device=d)
-        self.stats = torch.zeros(4, dtype=torch.int64, device=d)
+        self.stats = torch.zeros(8 if self.carousel else 4, dtype=torch.int64, device=d)
         if self.rule == "tc":
             self.tc = torch.zeros(*self.net.weights.shape, 2, dtype=torch.int64, device=d)
         if self.trace_len > 0:
@@ -197,13 +208,23 @@ class NTupleTrainer:
             nbytes = L.ntuple_lambda_workspace_bytes(n)
         else:
             nbytes = L.ntuple_tc_workspace_bytes(n) if self.rule == "tc" else L.ntuple_td_workspace_bytes(n)
+        if self.carousel:
+            self.pool = torch.zeros(self.net.num_stages, n, 16, dtype=torch.int8, device=d)
+            self.valid = torch.zeros(n, 16, dtype=torch.uint8, device=d)
+            self.next_stage = torch.zeros(n, dtype=torch.uint8, device=d)
+            self.origin = torch.zeros(n, dtype=torch.uint8, device=d)
+            nbytes = L.ntuple_carousel_workspace_bytes(n)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=d)
         L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
         self.counter = 1
 
     def _steps(self, steps: int) -> None:
         rng = L.make_rng(L.RNG_PHILOX, self.seed, self.counter)
-        if self.trace_len > 0:
+        if self.carousel:
+            L.ntuple_carousel(self.net.c, self.tc, self.boards, self.after, self.hist, self.hist_len, self.pending,
+                              self.run_score, steps, self.lr_shift, self.trace_len, self.lambda_shift, rng, self.pool,
+                              self.valid, self.next_stage, self.origin, self.stats, self.workspace)
+        elif self.trace_len > 0:
             L.ntuple_lambda(self.net.c, self.tc, self.boards, self.after, self.hist, self.hist_len, self.pending,
                             self.run_score, steps, self.lr_shift, self.trace_len, self.lambda_shift, rng, self.stats,
                             self.workspace)
@@ -241,9 +262,12 @@ class NTupleTrainer:
             steps -= k
             if P > 0 and (self.counter - 1) % P == 0:
                 promoted += self._cut()
-        games, score_sum, best, updates = self.stats.tolist()
-        return {"games": games, "mean_score": score_sum / games if games else 0.0, "max_score": best,
-                "updates": updates, "score_sum": score_sum, "promoted": promoted}
+        games, score_sum, best, updates, *car = self.stats.tolist()
+        out = {"games": games, "mean_score": score_sum / games if games else 0.0, "max_score": best,
+               "updates": updates, "score_sum": score_sum, "promoted": promoted}
+        if self.carousel:
+            out.update(zip(("restart_games", "restart_points", "recorded", "restarts"), car))
+        return out
 
     def accumulators(self):
         """-> (E, A): views int64 [T, 16^K] ([G, T, 16^K] with stages) of a weight's signed and absolute update sums under rule "tc" (A

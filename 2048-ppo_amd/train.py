@@ -413,14 +413,20 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
                  promote_every: int = typer.Option(0, "--promote-every", help="every P steps, start each stage a "
                                                                               "board has newly reached from the "
                                                                               "tables of the stage below it (needs "
-                                                                              "--stages); 0: never")):
+                                                                              "--stages); 0: never"),
+                 carousel: bool = typer.Option(False, "--carousel", help="restart finished games from boards with "
+                                                                         "which games entered each stage, going "
+                                                                         "round the stages in turn (needs "
+                                                                         "--stages)")):
     """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
     reproducible bit for bit.  Prints the games finished and their mean score per interval.  --rule tc
     keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, so resuming a TC
     run from a saved net is out of scope.  --trace H passes every error back along the last H
     after-states of its game, decayed by lambda = 2^-S (--lambda-shift S), under either rule.  --stages
     gives the net tables of its own for every stage of the game; --promote-every P adds, once per stage,
-    the tables of the stage below to it."""
+    the tables of the stage below to it; --carousel starts finished games from remembered boards of every
+    stage in turn, so that the late stages are trained as much as the first (the games and scores reported
+    stay those of full games from the empty board; restarts are counted beside them)."""
     from g2048.ntuple import MAX_LAMBDA_SHIFT, MAX_TRACE, PRESETS, NTupleNet, NTupleTrainer
     if tuples not in PRESETS:
         typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
@@ -446,22 +452,27 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
     if promote_every < 0 or (promote_every > 0 and not stage_list):
         typer.echo(f"Error: --promote-every must be 0, or positive with --stages, got {promote_every}")
         raise typer.Exit(1)
+    if carousel and not stage_list:
+        typer.echo("Error: --carousel needs --stages")
+        raise typer.Exit(1)
     if not torch.cuda.is_available():
         typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
         raise typer.Exit(1)
     net = NTupleNet(tuples, torch.device("cuda", 0), stages=stage_list)
-    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift, promote_every)
+    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift, promote_every, carousel)
     typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
                f"{net.weights.numel()} weights; stages {','.join(map(str, net.stages)) or 'none'}, "
                f"promote_every {promote_every}; {envs} envs, lr_shift {lr_shift}, trace {trace}, "
-               f"lambda_shift {lambda_shift}, rule {rule}")
+               f"lambda_shift {lambda_shift}, rule {rule}" + (", carousel" if carousel else ""))
     done = 0
     while done < steps:
         k = min(max(print_frequency, 1), steps - done)
         st = tr.train(k)
         done += k
         typer.echo(f"step {done}: games {st['games']}, mean score {st['mean_score']:.1f}, max {st['max_score']}, "
-                   f"updates {st['updates']}" + (f", promoted {st['promoted']}" if st["promoted"] else ""))
+                   f"updates {st['updates']}" + (f", promoted {st['promoted']}" if st["promoted"] else "") +
+                   (f", restarts {st['restarts']} (recorded {st['recorded']}, restarted games {st['restart_games']}, "
+                    f"their points {st['restart_points']})" if carousel else ""))
     if out is not None:
         out.parent.mkdir(parents=True, exist_ok=True)
         net.save(out)

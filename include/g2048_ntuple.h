@@ -6,7 +6,8 @@
  * the call), asynchronous on `stream`, no allocation and no host synchronisation (hipGraph-capturable),
  * 0 / G2048_EINVAL (nothing enqueued) / a positive hipError_t, n = 0 a no-op.  This text is the
  * specification; tests/ntuple_reference.py restates it, tests/ntuple_tc_reference.py the TC step,
- * tests/ntuple_lambda_reference.py the lambda step, tests/ntuple_stage_reference.py the stages.
+ * tests/ntuple_lambda_reference.py the lambda step, tests/ntuple_stage_reference.py the stages,
+ * tests/ntuple_carousel_reference.py the carousel.
  *
  * The network.  T tuples of K cells each (cell = 4 row + col) and one table of 16^K int32 weights per
  * tuple.  All values are integers: points x S, S = 2^G2048_NT_FRAC_BITS = 4096.
@@ -151,6 +152,47 @@
  * twin g2048_ntuple_staged_<call> that takes it and is otherwise the same call: the same arguments in the
  * same order, the same refusals (and an invalid map), the same workspace.  With stage_map == 0 a twin is
  * its one-stage call bit for bit.  C callers zero-initialise the struct (a designated initialiser does).
+ *
+ * Carousel (g2048_ntuple_staged_carousel; Jaskowski 2018, carousel shaping).  From the empty-board reset the
+ * tables of a late stage are updated only in the last moves of the few games that get that far.  The carousel
+ * remembers boards with which games entered each stage and starts finished games from them, going round the
+ * stages in turn, so that every stage's tables get a comparable share of the training.  The carousel step is
+ * the lambda step of a staged net with its step 3 extended; steps 1, 2 and 4, both rules and every trace_len
+ * are unchanged.  G is the number of stages, c + t the Philox counter of the step.  Carried beside boards /
+ * after / pending / hist, device memory, zero-filled at the start of a run and owned by the caller:
+ *   pool    int8 [G][n][16] (16-B aligned): pool[g][i] is the snapshot of stage g taken by env i; row 0 is
+ *           never read or written
+ *   valid   uint8 [n][16] (16-B aligned): valid[i][g] != 0 means pool[g][i] holds a snapshot
+ *   next    uint8 [n]: the stage at which env i's next game is to start, its place on the carousel
+ *   origin  uint8 [n]: the stage the current game of env i started from; 0: the ordinary reset
+ * Step 3 of the carousel step, for env i at step t:
+ *   3a. the env is stepped exactly as in the TD step (the action a*, or 0 without a legal move, AUTO_RESET,
+ *       counter c + t, env id env_base + i): b is the board before the step, b' the board after it, on DONE
+ *       the freshly reset board.
+ *   3b. not DONE and stage(b') != stage(b): the game has entered the stage g' = stage(b');
+ *       pool[g'][i] = b', valid[i][g'] = 1, stats[6] += 1.
+ *   3c. DONE: the game that ended is accounted.  origin[i] == 0: stats[0] += 1, stats[1] += run_score[i],
+ *       stats[2] = max(stats[2], run_score[i]), as in the TD step.  Otherwise stats[4] += 1 and stats[5] +=
+ *       run_score[i], the points since the restart: such a game is not a full game and stays out of the
+ *       score statistics.  run_score[i] = 0.  Then the next game is chosen:
+ *         j = (i + c + t) mod n     the donor slot: the sum modulo 2^64, i the local index
+ *         k = next[i] if next[i] < G, else 0
+ *         g = the smallest g' with max(k, 1) <= g' < G and valid[j][g'] != 0, if k >= 1 and there is one;
+ *             otherwise 0
+ *       g >= 1: boards[i] = pool[g][j] in place of the reset board, and stats[7] += 1; g == 0: the reset
+ *       board stays.  origin[i] = g, next[i] = (g + 1) mod G.
+ * Within one step the donors of the n envs are a permutation of the slots, so no two envs take the same one
+ * (except in a step whose sums pass 2^64 among its n envs, for an n that does not divide 2^64: slots are only
+ * read, so nothing depends on it), and the donor of an env moves on by one slot per step: the boards mix
+ * between the envs without a shared buffer filled by atomics, whose contents would depend on the order of
+ * arrival.
+ * Every read of pool and valid in a step sees them as they were before that step's writes: the rule of the TD
+ * step, extended.  next[i] is written by env i alone, so its choice is final before the step's writes.
+ * What follows: a game ended by DONE still gets pending = 2 and the terminal target 0; the restarted game
+ * starts with an empty trace (step 4 empties it for p != 1); with G = 1 nothing is ever recorded or restarted
+ * and the call is g2048_ntuple_staged_lambda bit for bit in every carried array, the weights, tc and
+ * stats[0..3]; a stage whose boards a game never enters (one the reset board is already in) is never
+ * recorded, and the carousel passes over it.  A run stays bitwise reproducible.
  */
 #ifndef G2048_NTUPLE_H
 #define G2048_NTUPLE_H
@@ -290,6 +332,28 @@ int g2048_ntuple_staged_lambda(g2048_stream_t stream, const g2048_ntuple_staged_
 int g2048_ntuple_staged_search(g2048_stream_t stream, const g2048_ntuple_staged_net *net, const int8_t *boards,
                                int64_t n, int64_t depth, int32_t form, int64_t *q, int64_t *leaves, uint8_t *legal,
                                uint8_t *best, void *workspace, size_t workspace_bytes);
+
+/* ---- the carousel (Carousel, above): the arrays carried beside those of the lambda step */
+typedef struct g2048_ntuple_carousel { /* host struct, read during the call; all device pointers */
+    int8_t *pool;    /* [G][n][16], 16-B aligned */
+    uint8_t *valid;  /* [n][16],    16-B aligned */
+    uint8_t *next;   /* [n] */
+    uint8_t *origin; /* [n] */
+} g2048_ntuple_carousel;
+
+/* `steps` carousel steps of n envs on a staged net: g2048_ntuple_staged_lambda's arguments in its order, its
+   refusals and its launches per step (two under rule TD, three under TC), and car.  stats (nullable) int64 [8]
+   = {full games finished, sum of their scores, largest of them, updates applied, restarted games finished,
+   sum of their points since the restart, snapshots recorded, restarts}: accumulated, not zeroed.  workspace:
+   g2048_ntuple_carousel_workspace_bytes(n) bytes (0 for an n the call would refuse).  In addition
+   G2048_EINVAL, with n > 0, for a null car, a null member of it, a misaligned pool or valid and a workspace
+   smaller than that. */
+size_t g2048_ntuple_carousel_workspace_bytes(int64_t n);
+int g2048_ntuple_staged_carousel(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int64_t *tc, int8_t *boards,
+                                 int8_t *after, int8_t *hist, uint8_t *hist_len, uint8_t *pending, int64_t *run_score,
+                                 int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
+                                 const g2048_rng *rng, const g2048_ntuple_carousel *car, int64_t *stats, void *workspace,
+                                 size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
