@@ -359,6 +359,24 @@ def ntuple_promote(net, src: int, dst: int, device=None):
           int(src), int(dst))
 
 
+def ntuple_promote_from(net, src: int, dst: int, base: int, device=None):
+    """W[dst] += W[src] - base, the promotion over the start `base` of the tables (g2048_ntuple_promote_from), on
+    torch's current stream of `device` as ntuple_promote."""
+    if not -(1 << 31) <= int(base) < 1 << 31:
+        raise G2048Error(f"ntuple_promote_from: base must be an int32, got {base}")
+    _call("g2048_ntuple_promote_from", ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream),
+          ctypes.byref(_staged(net)), int(src), int(dst), int(base))
+
+
+def ntuple_fill(net, w0: int, device=None):
+    """Every weight of the net = w0, any int32 (g2048_ntuple_fill, or its twin on a staged net), on torch's current
+    stream of `device` (the device of the net's weights; None: the current device)."""
+    w0 = int(w0)
+    if not -(1 << 31) <= w0 < 1 << 31:
+        raise G2048Error(f"ntuple_fill: w0 must be an int32, got {w0}")
+    _call(_nt_entry(net, "fill"), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), ctypes.byref(net), w0)
+
+
 def ntuple_value(net, boards, value):
     """value int64 [n] = V(boards[i]) (g2048_ntuple_value)."""
     n = boards.shape[0]

@@ -11,7 +11,11 @@ g2048_ntuple_tc), integer too.  With trace_len > 0 the error of an after-state i
 (or shifted by lambda_shift) per move, to the trace_len after-states before it: TD(lambda) / TC(lambda) with
 lambda = 2^-lambda_shift (g2048_ntuple_lambda).  With `stages` a net keeps one set of tables per stage of
 the game, the stage of a board given by its largest tile (Yeh et al. 2016; Jaskowski 2018), and the trainer's
-promote_every starts every stage from the tables of the one below it.  NTuplePlayer: the greedy
+promote_every starts every stage from the tables of the one below it.  With v_init every weight starts at
+w0_of(v_init, T) instead of zero, so that every board is worth v_init points until it is learned otherwise
+(optimistic initialisation, Guei et al. 2021: the exploration of a greedy learner; g2048_ntuple_fill), and
+promotion subtracts that start (g2048_ntuple_promote_from).  NTupleTrainer.save / load keep and continue a
+whole run, byte for byte the run that was not interrupted.  NTuplePlayer: the greedy
 player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
 search.py's game loop.
 """
@@ -32,6 +36,8 @@ MAX_ENVS = (1 << 28) - 1
 MAX_SEARCH_DEPTH = 3
 MAX_TRACE, MAX_LAMBDA_SHIFT = L.NT_MAX_TRACE, L.NT_MAX_LAMBDA_SHIFT
 MAX_STAGES = L.NT_MAX_STAGES
+MAX_W0 = 1 << 30
+TRAINER_FORMAT = "g2048-ntuple-trainer-1"
 
 
 def _check_cells(cells) -> list[list[int]]:
@@ -65,28 +71,55 @@ def stage_map_of(stages) -> int:
     return sum(sum(1 for v in stages if v <= 1 << m) << (4 * m) for m in range(1, 16))
 
 
+def w0_of(v_init: int, T: int) -> int:
+    """The start of every weight for an initial value of v_init points on a net of T tuples: v_init x 4096 /
+    (8 T), rounded to nearest, so that V(b) = 8 T w0 is v_init points x 4096 up to that rounding.  Raises for a
+    negative v_init and for a start above 2^30."""
+    v_init, T = int(v_init), int(T)
+    if not 1 <= T <= MAX_TUPLES:
+        raise ValueError(f"a net has 1..{MAX_TUPLES} tuples, got {T}")
+    if v_init < 0:
+        raise ValueError(f"v_init must not be negative, got {v_init}")
+    w0 = (v_init * (1 << FRAC_BITS) + 4 * T) // (8 * T)
+    if w0 > MAX_W0:
+        raise ValueError(f"v_init {v_init} on {T} tuples starts every weight at {w0}, above 2^30")
+    return w0
+
+
 class NTupleNet:
     """cells: a preset name or T tuples of K cell indices (4 row + col).  stages: strictly increasing tile
     values (powers of two in 2..32768); the stage of a board is the number of them that are <= its largest
     tile, and every stage has tables of its own (G = len(stages) + 1 of them).  weights: int32 [T, 16^K]
-    without stages, [G, T, 16^K] with them, on `device`, zero at the start (the greedy-on-points player)."""
+    without stages, [G, T, 16^K] with them, on `device`, zero at the start (the greedy-on-points player).
+    v_init (points): every weight starts at self.w0 = w0_of(v_init, T) instead, filled by the library on a GPU
+    device (g2048_ntuple_fill); with explicit weights w0 is only recorded, as the base that promote() subtracts."""
 
-    def __init__(self, cells="lines-squares-4", device="cuda", weights: torch.Tensor | None = None, stages=()):
+    def __init__(self, cells="lines-squares-4", device="cuda", weights: torch.Tensor | None = None, stages=(),
+                 v_init: int = 0):
         self.cells = _check_cells(cells)
+        self.w0 = w0_of(v_init, len(self.cells))
         self.device = torch.device(device)
         self.stages = _check_stages(stages)
         self.stage_map = stage_map_of(self.stages)
         shape = (len(self.cells), 16 ** len(self.cells[0]))
         if self.stages:
             shape = (len(self.stages) + 1,) + shape
-        if weights is None:
+        self._c = None
+        if weights is None and self.w0 == 0:
             weights = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        elif weights is None and self.device.type == "cuda":
+            self.weights = torch.empty(shape, dtype=torch.int32, device=self.device)
+            L.ntuple_fill(self.c, self.w0, self.device)
+            return
+        elif weights is None:  # a host net: there is no library call on the CPU
+            weights = torch.full(shape, self.w0, dtype=torch.int32, device=self.device)
         else:
+            if not isinstance(weights, torch.Tensor):
+                raise ValueError(f"weights must be an int32 tensor {shape}, got {type(weights).__name__}")
             if weights.dtype != torch.int32 or tuple(weights.shape) != shape:
                 raise ValueError(f"weights must be int32 {shape}, got {weights.dtype} {tuple(weights.shape)}")
             weights = weights.to(self.device).contiguous()
         self.weights = weights
-        self._c = None
 
     @property
     def c(self):
@@ -107,11 +140,15 @@ class NTupleNet:
         return out
 
     def promote(self, src: int, dst: int) -> None:
-        """Adds the tables of stage src to those of stage dst (int32, wrapping): a copy onto a zero stage."""
+        """Adds the tables of stage src, less the start w0, to those of stage dst (int32, wrapping): a copy onto a
+        stage that still holds w0 everywhere."""
         src, dst = int(src), int(dst)
         if not (0 <= src < self.num_stages and 0 <= dst < self.num_stages) or src == dst:
             raise ValueError(f"promote needs two different stages in 0..{self.num_stages - 1}, got {src} -> {dst}")
-        L.ntuple_promote(self.c, src, dst, self.device)
+        if self.w0 != 0:
+            L.ntuple_promote_from(self.c, src, dst, self.w0, self.device)
+        else:
+            L.ntuple_promote(self.c, src, dst, self.device)
 
     def value(self, boards: torch.Tensor) -> torch.Tensor:
         """V of boards int8 [n, 16] -> int64 [n] (points x 4096)."""
@@ -120,16 +157,28 @@ class NTupleNet:
         return out
 
     def save(self, path) -> None:
-        """cells and weights, and for a net with stages the key "stages"; a one-stage checkpoint is unchanged."""
+        """cells and weights, for a net with stages the key "stages" and for one with a start other than zero the
+        key "w0"; a one-stage or zero-start checkpoint is unchanged."""
         ck = {"cells": self.cells, "weights": self.weights.cpu()}
         if self.stages:
             ck["stages"] = list(self.stages)
+        if self.w0 != 0:
+            ck["w0"] = self.w0
         torch.save(ck, path)
 
     @classmethod
     def load(cls, path, device="cuda") -> "NTupleNet":
         ck = torch.load(path, map_location="cpu", weights_only=True)
-        return cls(ck["cells"], device, ck["weights"], ck.get("stages", ()))
+        return cls._with_w0(ck["cells"], device, ck["weights"], ck.get("stages", ()), ck.get("w0", 0))
+
+    @classmethod
+    def _with_w0(cls, cells, device, weights, stages, w0) -> "NTupleNet":
+        """A net of given weights whose recorded start is w0 itself, not that of a v_init."""
+        if isinstance(w0, bool) or not isinstance(w0, int) or not 0 <= w0 <= MAX_W0:
+            raise ValueError(f"w0 must be an int in [0, 2^30], got {w0!r}")
+        net = cls(cells, device, weights, stages)
+        net.w0 = w0
+        return net
 
 
 class NTupleTrainer:
@@ -140,8 +189,8 @@ class NTupleTrainer:
     every weight keeps the signed and the absolute sum of the updates it received (self.tc, int64
     [T, 16^K, 2], zero at the start: 16 bytes per weight on top of its 4) and takes the share
     |signed sum| / absolute sum of an update; lr_shift is then the base rate at which a fresh weight
-    starts.  The accumulators belong to the trainer, not to the net: NTupleNet.save keeps the net only,
-    and resuming a TC run from a saved net is out of scope (a new trainer starts from zero accumulators).
+    starts.  The accumulators belong to the trainer, not to the net: NTupleNet.save keeps the net only
+    (a new trainer on a saved net starts from zero accumulators); NTupleTrainer.save keeps them, below.
     trace_len in 0..4, lambda_shift in 1..7: with trace_len > 0 either rule runs as g2048_ntuple_lambda, and
     an update's D is also applied, shifted right by k lambda_shift (towards zero), to the after-state k
     moves older of the same game, k = 1..trace_len (self.hist int8 [trace_len, envs, 16], self.hist_len
@@ -159,9 +208,31 @@ class NTupleTrainer:
     g2048_ntuple_staged_carousel for every rule and trace.  train() then also returns restart_games and
     restart_points (finished games that started from a snapshot, and their points since), recorded (snapshots
     taken) and restarts; games / mean_score / max_score stay those of full games from the ordinary reset.  The
-    pool belongs to the trainer, like the accumulators.  False: exactly the calls above."""
+    pool belongs to the trainer, like the accumulators.  False: exactly the calls above.
+    state_dict() / from_state_dict() (save / load on top of them) keep a whole run: the net with its start w0,
+    the configuration, counter, promoted_upto and every carried tensor that exists, as one dict of CPU tensors,
+    ints, strings and lists (torch.load(weights_only=True) reads it); not the workspace, and not stats, which
+    train() zeroes per call.  A loaded trainer continues byte for byte as the saved one would have: the same
+    weights, accumulators, carried arrays and train() results, wherever the run was cut.  On load only lr_shift
+    and rule may differ from the saved run: "td" -> "tc" starts zero accumulators ("never updated": optimistic TD,
+    then TC fine-tuning on the same weights), "tc" -> "td" drops them."""
 
     RULES = ("td", "tc")
+    # the carried tensors of a started run: name -> (dtype, shape from (n, trace_len, G, weights shape))
+    _CARRIED = {
+        "boards": (torch.int8, lambda n, h, G, w: (n, 16)),
+        "after": (torch.int8, lambda n, h, G, w: (n, 16)),
+        "pending": (torch.uint8, lambda n, h, G, w: (n,)),
+        "run_score": (torch.int64, lambda n, h, G, w: (n,)),
+        "tc": (torch.int64, lambda n, h, G, w: w + (2,)),
+        "hist": (torch.int8, lambda n, h, G, w: (h, n, 16)),
+        "hist_len": (torch.uint8, lambda n, h, G, w: (n,)),
+        "pool": (torch.int8, lambda n, h, G, w: (G, n, 16)),
+        "valid": (torch.uint8, lambda n, h, G, w: (n, 16)),
+        "next_stage": (torch.uint8, lambda n, h, G, w: (n,)),
+        "origin": (torch.uint8, lambda n, h, G, w: (n,)),
+    }
+    _CONFIG = ("envs", "lr_shift", "seed", "rule", "trace_len", "lambda_shift", "promote_every", "carousel")
 
     def __init__(self, net: NTupleNet, envs: int = 256, lr_shift: int = 10, seed: int = 0x2048, rule: str = "td",
                  trace_len: int = 0, lambda_shift: int = 1, promote_every: int = 0, carousel: bool = False):
@@ -189,9 +260,22 @@ class NTupleTrainer:
         self.carousel = bool(carousel)
         self.pool = self.valid = self.next_stage = self.origin = None
         self.counter = 0
-        self.boards = None
+        self.boards = self.after = self.pending = self.run_score = None
         self.tc = None
         self.hist = self.hist_len = None
+        self.stats = self.workspace = None
+
+    def _scratch(self):
+        """What a checkpoint does not hold: stats and the workspace of the calls this configuration makes."""
+        d, n = self.net.device, self.envs
+        self.stats = torch.zeros(8 if self.carousel else 4, dtype=torch.int64, device=d)
+        if self.carousel:
+            nbytes = L.ntuple_carousel_workspace_bytes(n)
+        elif self.trace_len > 0:
+            nbytes = L.ntuple_lambda_workspace_bytes(n)
+        else:
+            nbytes = L.ntuple_tc_workspace_bytes(n) if self.rule == "tc" else L.ntuple_td_workspace_bytes(n)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=d)
 
     def _start(self):
         d, n = self.net.device, self.envs
@@ -199,22 +283,16 @@ class NTupleTrainer:
         self.after = torch.zeros(n, 16, dtype=torch.int8, device=d)
         self.pending = torch.zeros(n, dtype=torch.uint8, device=d)
         self.run_score = torch.zeros(n, dtype=torch.int64, device=d)
-        self.stats = torch.zeros(8 if self.carousel else 4, dtype=torch.int64, device=d)
         if self.rule == "tc":
             self.tc = torch.zeros(*self.net.weights.shape, 2, dtype=torch.int64, device=d)
         if self.trace_len > 0:
             self.hist = torch.zeros(self.trace_len, n, 16, dtype=torch.int8, device=d)
             self.hist_len = torch.zeros(n, dtype=torch.uint8, device=d)
-            nbytes = L.ntuple_lambda_workspace_bytes(n)
-        else:
-            nbytes = L.ntuple_tc_workspace_bytes(n) if self.rule == "tc" else L.ntuple_td_workspace_bytes(n)
         if self.carousel:
             self.pool = torch.zeros(self.net.num_stages, n, 16, dtype=torch.int8, device=d)
             self.valid = torch.zeros(n, 16, dtype=torch.uint8, device=d)
             self.next_stage = torch.zeros(n, dtype=torch.uint8, device=d)
             self.origin = torch.zeros(n, dtype=torch.uint8, device=d)
-            nbytes = L.ntuple_carousel_workspace_bytes(n)
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=d)
         L.env_reset(self.boards, None, L.make_rng(L.RNG_PHILOX, self.seed, 0))
         self.counter = 1
 
@@ -254,6 +332,8 @@ class NTupleTrainer:
             raise ValueError(f"steps must be positive, got {steps}")
         if self.boards is None:
             self._start()
+        if self.workspace is None:  # the first call, of a new run or of a loaded one
+            self._scratch()
         self.stats.zero_()
         promoted, P = [], self.promote_every
         while steps > 0:
@@ -277,6 +357,93 @@ class NTupleTrainer:
         if self.tc is None:
             return None, None
         return self.tc[..., 0], self.tc[..., 1]
+
+    def _carried_names(self, rule: str) -> list[str]:
+        """The carried tensors a started run of this configuration holds under `rule`."""
+        names = ["boards", "after", "pending", "run_score"]
+        if rule == "tc":
+            names.append("tc")
+        if self.trace_len > 0:
+            names += ["hist", "hist_len"]
+        if self.carousel:
+            names += ["pool", "valid", "next_stage", "origin"]
+        return names
+
+    def state_dict(self) -> dict:
+        """The whole run as one dict of CPU tensors, ints, strings and lists (the class docstring); with a
+        device net it reads the device.  The tensors are copies."""
+        def host(t):
+            return t.cpu() if t.is_cuda else t.clone()
+
+        net = self.net
+        sd = {"format": TRAINER_FORMAT, "cells": [list(t) for t in net.cells], "stages": list(net.stages),
+              "w0": net.w0, "weights": host(net.weights), "envs": self.envs, "lr_shift": self.lr_shift,
+              "seed": self.seed, "rule": self.rule, "trace_len": self.trace_len, "lambda_shift": self.lambda_shift,
+              "promote_every": self.promote_every, "carousel": self.carousel, "counter": self.counter,
+              "promoted_upto": self.promoted_upto}
+        if self.boards is not None:
+            for k in self._carried_names(self.rule):
+                sd[k] = host(getattr(self, k))
+        return sd
+
+    @classmethod
+    def from_state_dict(cls, sd: dict, device="cuda", rule: str | None = None, lr_shift: int | None = None,
+                        **other) -> "NTupleTrainer":
+        """A new net (trainer.net) and trainer on `device` that continue the run of a state_dict().  rule and
+        lr_shift, when given, replace the saved ones (the class docstring); nothing else may differ.  Raises
+        ValueError for an unknown format, a missing or surplus entry and a tensor whose dtype or shape does not
+        fit the saved configuration.  Makes no library call: the first train() does."""
+        if other:
+            raise ValueError(f"only rule and lr_shift may differ from the saved run, got {sorted(other)}")
+        if not isinstance(sd, dict) or sd.get("format") != TRAINER_FORMAT:
+            raise ValueError(f"not a checkpoint of an n-tuple trainer (format {TRAINER_FORMAT!r}): got "
+                             f"{sd.get('format') if isinstance(sd, dict) else type(sd).__name__!r}")
+        need = ("cells", "stages", "w0", "weights", "counter", "promoted_upto") + cls._CONFIG
+        missing = [k for k in need if k not in sd]
+        if missing:
+            raise ValueError(f"the checkpoint lacks {missing}")
+        for k in ("envs", "lr_shift", "seed", "trace_len", "lambda_shift", "promote_every", "counter", "promoted_upto"):
+            if isinstance(sd[k], bool) or not isinstance(sd[k], int):
+                raise ValueError(f"{k} must be an int, got {sd[k]!r}")
+        if not isinstance(sd["carousel"], bool):
+            raise ValueError(f"carousel must be a bool, got {sd['carousel']!r}")
+        if sd["rule"] not in cls.RULES:
+            raise ValueError(f"rule must be one of {cls.RULES}, got {sd['rule']!r}")
+        net = NTupleNet._with_w0(sd["cells"], device, sd["weights"], sd["stages"], sd["w0"])
+        tr = cls(net, sd["envs"], sd["lr_shift"] if lr_shift is None else lr_shift, sd["seed"],
+                 sd["rule"] if rule is None else rule, sd["trace_len"], sd["lambda_shift"], sd["promote_every"],
+                 sd["carousel"])
+        counter, upto = sd["counter"], sd["promoted_upto"]
+        if counter < 0 or not 0 <= upto < net.num_stages or (counter == 0 and upto != 0):
+            raise ValueError(f"counter {counter} and promoted_upto {upto} do not fit a run of {net.num_stages} stages")
+        saved = tr._carried_names(sd["rule"]) if counter > 0 else []
+        known = set(need) | {"format"} | set(cls._CARRIED)
+        surplus = [k for k in sd if k not in known or (k in cls._CARRIED and k not in saved)]
+        if surplus:
+            raise ValueError(f"the checkpoint holds {surplus}, which a run of its configuration does not carry")
+        dims = (tr.envs, tr.trace_len, net.num_stages, tuple(net.weights.shape))
+        for k in saved:
+            dtype, shape = cls._CARRIED[k][0], cls._CARRIED[k][1](*dims)
+            t = sd.get(k)
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+                got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else repr(type(t).__name__)
+                raise ValueError(f"{k} must be {dtype} {shape}, got {got}")
+        for k in saved:
+            if k != "tc" or tr.rule == "tc":  # "tc" -> "td" drops the accumulators
+                setattr(tr, k, sd[k].contiguous().to(net.device, copy=True))
+        if counter > 0 and tr.rule == "tc" and tr.tc is None:  # "td" -> "tc": never updated, the base rate
+            tr.tc = torch.zeros(*net.weights.shape, 2, dtype=torch.int64, device=net.device)
+        tr.counter, tr.promoted_upto = counter, upto
+        return tr
+
+    def save(self, path) -> None:
+        """state_dict() to a file.  The accumulators of rule "tc" are 16 bytes per weight beside its 4: 4x6 with four
+        stages is about 5 GB."""
+        torch.save(self.state_dict(), path)
+
+    @classmethod
+    def load(cls, path, device="cuda", rule: str | None = None, lr_shift: int | None = None) -> "NTupleTrainer":
+        return cls.from_state_dict(torch.load(path, map_location="cpu", weights_only=True), device, rule, lr_shift)
 
 
 class NTuplePlayer(_SearchPlayer):

@@ -388,7 +388,8 @@ def play_expectimax(games: int = typer.Option(100, "--games", "-g"),
 
 
 @app.command("train-ntuple")
-def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD steps of every env"),
+def train_ntuple(ctx: typer.Context,
+                 steps: int = typer.Option(10000, "--steps", "-s", help="TD steps of every env"),
                  envs: int = typer.Option(256, "--envs", help="games learning in parallel on the one net"),
                  lr_shift: int = typer.Option(10, "--lr-shift", help="an update adds delta / 2^lr_shift (1..30); "
                                                                     "raise it with --envs.  Under --rule tc the "
@@ -417,17 +418,50 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
                  carousel: bool = typer.Option(False, "--carousel", help="restart finished games from boards with "
                                                                          "which games entered each stage, going "
                                                                          "round the stages in turn (needs "
-                                                                         "--stages)")):
+                                                                         "--stages)"),
+                 v_init: int = typer.Option(0, "--v-init", help="optimistic initialisation: every board starts "
+                                                                "worth this many points (every weight at "
+                                                                "POINTS x 4096 / (8 T), rounded), and promotion "
+                                                                "takes that start off; 0: zero tables"),
+                 checkpoint: Optional[Path] = typer.Option(None, "--checkpoint", help="where to save the whole run "
+                                                                                      "at the end (net, accumulators, "
+                                                                                      "games in progress, counter), "
+                                                                                      "for --resume; 4x6 with four "
+                                                                                      "stages under --rule tc is "
+                                                                                      "about 5 GB"),
+                 resume: Optional[Path] = typer.Option(None, "--resume", help="continue the run saved by "
+                                                                              "--checkpoint for --steps more steps, "
+                                                                              "byte for byte as if it had not "
+                                                                              "stopped; only --rule and --lr-shift "
+                                                                              "may be given anew")):
     """Train an n-tuple network by afterstate TD(0) on the device: integer weights, so a run is
     reproducible bit for bit.  Prints the games finished and their mean score per interval.  --rule tc
-    keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, so resuming a TC
-    run from a saved net is out of scope.  --trace H passes every error back along the last H
+    keeps 16 bytes of accumulators per weight beside the net; --out saves the net only, --checkpoint the
+    whole run, which --resume continues (a checkpoint of 4x6 with four stages under --rule tc is about 5 GB).
+    --v-init V starts every board at V points (optimistic initialisation: the greedy learner then tries what
+    it has not seen); the two-phase recipe is `--v-init V --rule td --checkpoint a.pt`, then `--resume a.pt
+    --rule tc`: TC fine-tuning of the same weights from fresh accumulators.  --trace H passes every error back along the last H
     after-states of its game, decayed by lambda = 2^-S (--lambda-shift S), under either rule.  --stages
     gives the net tables of its own for every stage of the game; --promote-every P adds, once per stage,
     the tables of the stage below to it; --carousel starts finished games from remembered boards of every
     stage in turn, so that the late stages are trained as much as the first (the games and scores reported
     stay those of full games from the empty board; restarts are counted beside them)."""
-    from g2048.ntuple import MAX_LAMBDA_SHIFT, MAX_TRACE, PRESETS, NTupleNet, NTupleTrainer
+    from g2048.ntuple import MAX_LAMBDA_SHIFT, MAX_TRACE, PRESETS, NTupleNet, NTupleTrainer, w0_of
+    # the options given on the command line, as opposed to defaults (compared by name: the enum's home differs
+    # between versions of the command-line library)
+    given = {name for name in ctx.params if getattr(ctx.get_parameter_source(name), "name", "") == "COMMANDLINE"}
+    if resume is not None:
+        fixed = {"envs": "--envs", "tuples": "--tuples", "seed": "--seed", "trace": "--trace",
+                 "lambda_shift": "--lambda-shift", "stages": "--stages", "promote_every": "--promote-every",
+                 "carousel": "--carousel", "v_init": "--v-init"}
+        clash = sorted(opt for name, opt in fixed.items() if name in given)
+        if clash:
+            typer.echo(f"Error: --resume continues the saved run: {', '.join(clash)} cannot be given with it "
+                       f"(only --rule and --lr-shift can)")
+            raise typer.Exit(1)
+        if not resume.is_file():
+            typer.echo(f"Error: --resume: no such file {resume}")
+            raise typer.Exit(1)
     if tuples not in PRESETS:
         typer.echo(f"Unknown tuple preset: {tuples}. Use one of {', '.join(sorted(PRESETS))}.")
         raise typer.Exit(1)
@@ -455,16 +489,38 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
     if carousel and not stage_list:
         typer.echo("Error: --carousel needs --stages")
         raise typer.Exit(1)
+    try:
+        w0 = w0_of(v_init, len(PRESETS[tuples]))
+    except ValueError as e:
+        typer.echo(f"Error: --v-init: {e}")
+        raise typer.Exit(1)
     if not torch.cuda.is_available():
         typer.echo("Error: no ROCm GPU visible; the n-tuple trainer has no CPU path")
         raise typer.Exit(1)
-    net = NTupleNet(tuples, torch.device("cuda", 0), stages=stage_list)
-    tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift, promote_every, carousel)
+    if resume is not None:
+        try:
+            tr = NTupleTrainer.load(resume, torch.device("cuda", 0), rule if "rule" in given else None,
+                                    lr_shift if "lr_shift" in given else None)
+        except Exception as e:  # not a checkpoint of this trainer, or one that does not fit itself
+            typer.echo(f"Error: --resume {resume}: {e}")
+            raise typer.Exit(1)
+        net, w0 = tr.net, tr.net.w0
+        tuples = next((name for name, cells in PRESETS.items() if cells == net.cells), "custom")
+        envs, lr_shift, rule, trace, lambda_shift = tr.envs, tr.lr_shift, tr.rule, tr.trace_len, tr.lambda_shift
+        promote_every, carousel = tr.promote_every, tr.carousel
+    else:
+        net = NTupleNet(tuples, torch.device("cuda", 0), stages=stage_list, v_init=v_init)
+        tr = NTupleTrainer(net, envs, lr_shift, seed, rule, trace, lambda_shift, promote_every, carousel)
     typer.echo(f"n-tuple net {tuples}: {len(net.cells)} tuples of {len(net.cells[0])} cells, "
                f"{net.weights.numel()} weights; stages {','.join(map(str, net.stages)) or 'none'}, "
                f"promote_every {promote_every}; {envs} envs, lr_shift {lr_shift}, trace {trace}, "
-               f"lambda_shift {lambda_shift}, rule {rule}" + (", carousel" if carousel else ""))
-    done = 0
+               f"lambda_shift {lambda_shift}, rule {rule}" +
+               (f", v_init {v_init} (w0 {w0})" if resume is None and v_init != 0 else "") +
+               (f", w0 {w0}" if resume is not None and w0 != 0 else "") + (", carousel" if carousel else ""))
+    done = max(tr.counter - 1, 0)  # the steps of the saved run; 0 for a new one
+    if resume is not None:
+        typer.echo(f"Resumed {resume} after step {done}")
+    steps += done
     while done < steps:
         k = min(max(print_frequency, 1), steps - done)
         st = tr.train(k)
@@ -477,6 +533,10 @@ def train_ntuple(steps: int = typer.Option(10000, "--steps", "-s", help="TD step
         out.parent.mkdir(parents=True, exist_ok=True)
         net.save(out)
         typer.echo(f"Saved the net to {out}")
+    if checkpoint is not None:
+        checkpoint.parent.mkdir(parents=True, exist_ok=True)
+        tr.save(checkpoint)
+        typer.echo(f"Saved the run to {checkpoint}")
 
 
 @app.command("play-ntuple")

@@ -193,6 +193,26 @@
  * and the call is g2048_ntuple_staged_lambda bit for bit in every carried array, the weights, tc and
  * stats[0..3]; a stage whose boards a game never enters (one the reset board is already in) is never
  * recorded, and the carousel passes over it.  A run stays bitwise reproducible.
+ *
+ * Optimistic initialisation (g2048_ntuple_fill, g2048_ntuple_promote_from; Guei, Chen, Wu 2021, "Optimistic
+ * Temporal Difference Learning for 2048"; tests/ntuple_optimistic_reference.py).  The learner is greedy: it plays
+ * the move of the largest q and never explores.  From zero tables a board never seen is worth nothing, less than
+ * any board that has scored, and is never tried.  Starting every weight at one positive value turns that round:
+ * every board is worth the same large V_init until the terminal target 0 and the rewards really seen pull the
+ * boards a game visits down, so a board not yet visited looks better than a visited one and gets its turn.
+ *   fill:  W[j] = w0 for every j < T 16^K (a staged net: every j < G T 16^K, all stages), any int32 w0.
+ * Consequence: V(b) = 8 T w0 for every board b, multiplicities included (a self-symmetric tuple reads its one
+ * weight twice, and both reads give w0), at every stage.  So q[a] = S pts(b, a) + 8 T w0 for every legal a: on a
+ * board whose legal moves merge nothing (or the same points) they all tie, and best is the lowest legal index.
+ * For V_init points the start is w0 = round(V_init S / (8 T)); the learning steps do not know of it: they run
+ * from these tables exactly as from any others.  fill writes nothing outside the tables and leaves tc alone.
+ * Promotion of g2048_ntuple_promote adds a whole stage, start included: onto a stage that still holds w0
+ * everywhere it would leave W[from] + w0, the optimism doubled.  The promotion over a start takes it off:
+ *   promote_from:  W[to][j] += W[from][j] - base  for every j < T 16^K, int32 and wrapping like every add on the
+ *                  weights (the difference and the sum both modulo 2^32).
+ * With base == 0 it is g2048_ntuple_promote byte for byte.  On a stage that still holds base everywhere it is a
+ * copy of W[from]; on one that has learned d[j] over base it leaves base + d[j] + (W[from][j] - base): what both
+ * stages learned, over one start.  The accumulators of rule TC are not touched, as in g2048_ntuple_promote.
  */
 #ifndef G2048_NTUPLE_H
 #define G2048_NTUPLE_H
@@ -354,6 +374,17 @@ int g2048_ntuple_staged_carousel(g2048_stream_t stream, const g2048_ntuple_stage
                                  int64_t n, int64_t steps, int32_t lr_shift, int32_t trace_len, int32_t lambda_shift,
                                  const g2048_rng *rng, const g2048_ntuple_carousel *car, int64_t *stats, void *workspace,
                                  size_t workspace_bytes);
+
+/* ---- optimistic initialisation (Optimistic initialisation, above).  fill: W[j] = w0 for every weight of the net,
+   j < T 16^K (staged: j < G T 16^K), one launch; any int32 w0; nothing outside the tables is written.
+   G2048_EINVAL for a net g2048_ntuple_weight_count (staged: g2048_ntuple_staged_weight_count) refuses. */
+int g2048_ntuple_fill(g2048_stream_t stream, const g2048_ntuple_net *net, int32_t w0);
+int g2048_ntuple_staged_fill(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int32_t w0);
+
+/* Promotion over a start: W[to][j] += W[from][j] - base for every j < T 16^K, one launch; any int32 base, base 0
+   is g2048_ntuple_promote.  The refusals are g2048_ntuple_promote's. */
+int g2048_ntuple_promote_from(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int32_t from, int32_t to,
+                              int32_t base);
 
 #ifdef __cplusplus
 }
