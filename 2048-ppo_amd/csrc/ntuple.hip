@@ -23,7 +23,9 @@
 // kernels instantiated with S = true beside the one-stage ones.  nt_stage_kernel writes the stages of
 // boards, nt_promote_kernel adds one stage's tables to another's (g2048_ntuple_promote).  nt_fill_kernel starts
 // every weight of a net at one value (optimistic initialisation, g2048_ntuple_fill) and nt_promote_from_kernel
-// is the promotion that takes that start off what it adds (g2048_ntuple_promote_from).
+// is the promotion that takes that start off what it adds (g2048_ntuple_promote_from).  nt_downgrade_kernel is
+// the players' tile-downgrading (g2048_ntuple_downgrade): a board-to-board map in front of the choose and search
+// calls, which stay as they are.
 // The carousel (g2048_ntuple_staged_carousel) is a third switch, C, on the reading kernel and on the last
 // one: a finished game restarts from a board with which some game entered a stage, out of a pool of one
 // slot per (stage, env).  The reading kernel picks every env's donor slot and start stage and leaves them in
@@ -153,6 +155,49 @@ __global__ __launch_bounds__(256) void nt_promote_from_kernel(const uint4 *__res
         t.w += f.w - base;
         to[j] = t;
     }
+}
+
+// Tile-downgrading (Tile-downgrading of include/g2048_ntuple.h): one board per lane, in nt_stage_kernel's shape.
+// The 16 bytes give the presence mask P (bit u for a cell 1 <= u <= 31); a round finds the largest tile m and the
+// largest absent value j in [lo, m) by clz on the mask, moves the mask's bits above j down by one and takes one
+// off every byte with j < u <= 31 of the four words (a carry-free byte-wise compare: bit 7 of (u & 0x7F) + 0x7F - j
+// is u > j for u <= 127, and `small` marks the bytes <= 31, which a round never changes).  boards and out may be
+// the same array, so neither is __restrict__: a lane reads its board before it writes it, and no other lane's.
+__global__ __launch_bounds__(256) void nt_downgrade_kernel(const uint4 *boards, uint4 *out, uint8_t *__restrict__ shift,
+                                                           uint32_t n, uint32_t from_exp, uint32_t lo_exp,
+                                                           uint32_t rounds) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 b = boards[i];
+    uint32_t w[4] = {b.x, b.y, b.z, b.w};
+    uint32_t small[4];  // 0x01 in every byte <= 31
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t hi = w[k] & 0xE0E0E0E0u;
+        small[k] = (~(((hi & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | hi) & 0x80808080u) >> 7;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint32_t u = (w[k] >> (8 * c)) & 0xFFu;
+            mask |= u < 32u ? 1u << u : 0u;
+        }
+    }
+    mask &= ~1u;  // an empty cell is no value
+    uint32_t done = 0u;
+    for (; done < rounds; done++) {
+        if (mask == 0u) break;
+        const uint32_t m = 31u - (uint32_t)__clz((int)mask);
+        if (m < from_exp) break;
+        const uint32_t absent = ~mask & ((1u << m) - 1u) & ~((1u << lo_exp) - 1u);  // lo <= j < m, not in P
+        if (absent == 0u) break;
+        const uint32_t j = 31u - (uint32_t)__clz((int)absent);  // 1 <= j <= 30
+        mask = (mask & ((1u << j) - 1u)) | ((mask >> (j + 1u)) << j);
+        const uint32_t add = (0x7Fu - j) * 0x01010101u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] -= ((((w[k] & 0x7F7F7F7Fu) + add) >> 7) & small[k]);
+    }
+    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+    if (shift) shift[i] = (uint8_t)done;
 }
 
 // The carousel's kernel arguments (Carousel of include/g2048_ntuple.h), last in the list of the two kernels
@@ -568,6 +613,18 @@ int g2048_ntuple_staged_fill(g2048_stream_t stream, const g2048_ntuple_staged_ne
     NtArgs a;
     if (!snet || !make_args(&snet->net, snet->stage_map, a)) return G2048_EINVAL;
     return nt_fill(stream, a, ((size_t)a.G * snet->net.num_tuples) << (4 * snet->net.tuple_len), w0);
+}
+
+int g2048_ntuple_downgrade(g2048_stream_t stream, const int8_t *boards, int8_t *out, uint8_t *shift, int64_t n,
+                           int32_t from_exp, int32_t lo_exp, int32_t rounds) {
+    if (from_exp < 2 || from_exp > 31 || lo_exp < 1 || lo_exp >= from_exp || rounds < 1 || rounds > 16) return G2048_EINVAL;
+    if (n < 0 || n >= (int64_t(1) << 31)) return G2048_EINVAL;
+    if (n == 0) return G2048_OK;
+    if (!boards || !aligned16(boards) || !out || !aligned16(out)) return G2048_EINVAL;
+    hipLaunchKernelGGL(nt_downgrade_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint4 *)boards, (uint4 *)out, shift, (uint32_t)n, (uint32_t)from_exp, (uint32_t)lo_exp,
+                       (uint32_t)rounds);
+    return launch_status();
 }
 
 static int nt_call_value(g2048_stream_t stream, const g2048_ntuple_net *net, uint64_t stage_map, const int8_t *boards,

@@ -351,6 +351,18 @@ def ntuple_stage(net, boards, out):
           _dev(out, torch.uint8, "out"), n)
 
 
+def ntuple_downgrade(boards, out, shift, from_exp: int, lo_exp: int, rounds: int):
+    """out int8 [n, 16] = boards after at most `rounds` rounds of tile-downgrading, shift uint8 [n] (or None) the
+    rounds applied (g2048_ntuple_downgrade).  out may be boards itself."""
+    n = boards.shape[0]
+    if out is None or out.numel() < 16 * n:
+        raise G2048Error(f"ntuple_downgrade: out holds {None if out is None else out.numel()} elements, needs {16 * n}")
+    if shift is not None and shift.numel() < n:
+        raise G2048Error(f"ntuple_downgrade: shift holds {shift.numel()} elements, needs {n}")
+    _call("g2048_ntuple_downgrade", _stream(boards), _dev(boards, torch.int8, "boards"), _dev(out, torch.int8, "out"),
+          _dev(shift, torch.uint8, "shift"), n, int(from_exp), int(lo_exp), int(rounds))
+
+
 def ntuple_promote(net, src: int, dst: int, device=None):
     """W[dst] += W[src], the tables of two stages of the net (g2048_ntuple_promote), on torch's current stream
     of `device` (the device of the net's weights; None: the current device)."""

@@ -17,10 +17,14 @@ w0_of(v_init, T) instead of zero, so that every board is worth v_init points unt
 promotion subtracts that start (g2048_ntuple_promote_from).  NTupleTrainer.save / load keep and continue a
 whole run, byte for byte the run that was not interrupted.  NTuplePlayer: the greedy
 player of a net (g2048_ntuple_choose) or, with depth 2..3, its expectimax player (g2048_ntuple_search) in
-search.py's game loop.
+search.py's game loop; with `downgrade` it chooses on the tile-downgraded board (downgrade_boards,
+g2048_ntuple_downgrade; Guei et al. 2021): the tiles above a missing value halved, so that a board with tiles the
+net has hardly seen becomes one it knows.
 """
 
 from __future__ import annotations
+
+import operator
 
 import torch
 
@@ -37,6 +41,7 @@ MAX_SEARCH_DEPTH = 3
 MAX_TRACE, MAX_LAMBDA_SHIFT = L.NT_MAX_TRACE, L.NT_MAX_LAMBDA_SHIFT
 MAX_STAGES = L.NT_MAX_STAGES
 MAX_W0 = 1 << 30
+MAX_DOWNGRADE_ROUNDS = 16
 TRAINER_FORMAT = "g2048-ntuple-trainer-1"
 
 
@@ -84,6 +89,51 @@ def w0_of(v_init: int, T: int) -> int:
     if w0 > MAX_W0:
         raise ValueError(f"v_init {v_init} on {T} tuples starts every weight at {w0}, above 2^30")
     return w0
+
+
+def downgrade_params(from_tile, lo_tile=2, rounds=1) -> tuple[int, int, int]:
+    """(from_tile, lo_tile, rounds) as tile values -> (from_exp, lo_exp, rounds) of g2048_ntuple_downgrade.  Each is
+    an integer (a Python int, or what operator.index takes, such as a numpy integer); a bool, a float or a string
+    raises ValueError like a value out of range."""
+    def integer(v, name):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            return operator.index(v)
+        except TypeError:
+            raise ValueError(f"{name} must be an integer, got {v!r}") from None
+
+    def tile(v, name):
+        v = integer(v, name)
+        if v < 2 or v & (v - 1):
+            raise ValueError(f"{name} must be a tile value (a power of two), got {v!r}")
+        return v.bit_length() - 1
+
+    f, l, rounds = tile(from_tile, "from_tile"), tile(lo_tile, "lo_tile"), integer(rounds, "rounds")
+    if not 2 <= f <= 15:
+        raise ValueError(f"from_tile must be a power of two in 4..32768, got {from_tile}")
+    if not 1 <= l < f:
+        raise ValueError(f"lo_tile must be a power of two in 2..from_tile / 2 = {(1 << f) // 2}, got {lo_tile}")
+    if not 1 <= rounds <= MAX_DOWNGRADE_ROUNDS:
+        raise ValueError(f"rounds must be in [1, {MAX_DOWNGRADE_ROUNDS}], got {rounds!r}")
+    return f, l, rounds
+
+
+def downgrade_boards(boards: torch.Tensor, from_tile: int, lo_tile: int = 2, rounds: int = 1,
+                     out: torch.Tensor | None = None):
+    """Tile-downgrading (Tile-downgrading of include/g2048_ntuple.h) of boards int8 [n, 16] -> (boards' int8 [n, 16],
+    shift uint8 [n]).  A board whose largest tile is at least from_tile and that lacks a tile value in lo_tile ..
+    below its largest has every tile above the largest such gap halved; that is one round, and at most `rounds` are
+    applied, shift counting them.  Empty cells, the tiles up to the gap, the order between any two cells and so
+    the legal moves are kept; merge points are not.  out: where to write (boards itself is allowed); None: a new
+    tensor.  Raises ValueError for tiles that are no powers of two, from_tile outside 4..32768, lo_tile outside
+    2..from_tile / 2 and rounds outside 1..16."""
+    f, l, rounds = downgrade_params(from_tile, lo_tile, rounds)
+    if out is None:
+        out = torch.empty_like(boards)
+    shift = torch.empty(boards.shape[0], dtype=torch.uint8, device=boards.device)
+    L.ntuple_downgrade(boards, out, shift, f, l, rounds)
+    return out, shift
 
 
 class NTupleNet:
@@ -450,9 +500,14 @@ class NTuplePlayer(_SearchPlayer):
     """Plays the move of the largest points + V(after-state) of `net` (depth 1, g2048_ntuple_choose) or of
     the largest expectimax value over `depth` in 2..3 moves, the root move included, with V at the leaves
     (g2048_ntuple_search; form "auto" / "narrow" / "wide": the lane mapping, the results do not depend on
-    it).  It draws nothing."""
+    it).  It draws nothing.
+    downgrade: None, or (from_tile, lo_tile, rounds) as downgrade_boards takes them: every search then runs on the
+    tile-downgraded boards (one more launch and an int8 [n, 16] buffer per search), for a staged net at the stage of
+    the translated board.  The legal moves of the two boards are the same, so the move chosen is a legal move of
+    the board given; q are the values of the translated board (its merge points are those of halved tiles): they
+    rank its moves and are not scores of the original.  None is the player without it: no buffer, no launch."""
 
-    def __init__(self, net: NTupleNet, depth: int = 1, form: str = "auto"):
+    def __init__(self, net: NTupleNet, depth: int = 1, form: str = "auto", downgrade=None):
         if not isinstance(net, NTupleNet):
             raise ValueError(f"NTuplePlayer needs an NTupleNet, got {type(net).__name__}")
         depth = int(depth)
@@ -462,6 +517,12 @@ class NTuplePlayer(_SearchPlayer):
             raise ValueError(f"form must be one of {sorted(EMAX_FORMS)}, got {form!r}")
         if form == "wide" and depth < 2:
             raise ValueError("form 'wide' needs depth >= 2")
+        self.downgrade = self._downgrade_exps = None  # the triple as given (tile values), and as the library takes it
+        if downgrade is not None:
+            if not isinstance(downgrade, (tuple, list)) or len(downgrade) != 3:
+                raise ValueError(f"downgrade must be None or (from_tile, lo_tile, rounds), got {downgrade!r}")
+            f, l, rounds = self._downgrade_exps = downgrade_params(*downgrade)
+            self.downgrade = (1 << f, 1 << l, rounds)
         self.net, self.depth, self.form = net, depth, form
         self.device = net.device
 
@@ -469,14 +530,19 @@ class NTuplePlayer(_SearchPlayer):
         d = self.device
         bufs = (torch.empty(n, dtype=torch.uint8, device=d), torch.empty(n, 4, dtype=torch.int64, device=d),
                 torch.empty(n, dtype=torch.uint8, device=d))
-        if self.depth == 1:
-            return bufs
-        nbytes = L.ntuple_search_workspace_bytes(n, self.depth, EMAX_FORMS[self.form])
-        if nbytes == 0:
-            raise ValueError(f"{n} boards are too many for form {self.form!r}")
-        return bufs + (torch.empty(nbytes, dtype=torch.uint8, device=d),)
+        if self.depth > 1:
+            nbytes = L.ntuple_search_workspace_bytes(n, self.depth, EMAX_FORMS[self.form])
+            if nbytes == 0:
+                raise ValueError(f"{n} boards are too many for form {self.form!r}")
+            bufs += (torch.empty(nbytes, dtype=torch.uint8, device=d),)
+        if self.downgrade is not None:  # the translated boards, last
+            bufs += (torch.empty(n, 16, dtype=torch.int8, device=d),)
+        return bufs
 
     def _search(self, boards, move_index: int, bufs):
+        if self.downgrade is not None:
+            L.ntuple_downgrade(boards, bufs[-1], None, *self._downgrade_exps)
+            boards, bufs = bufs[-1], bufs[:-1]
         if self.depth == 1:
             best, q, legal = bufs
             L.ntuple_choose(self.net.c, boards, q, legal, best)
@@ -486,7 +552,8 @@ class NTuplePlayer(_SearchPlayer):
 
     def choose(self, boards: torch.Tensor):
         """boards int8 [n, 16] -> (best uint8 [n] (0xFF: no legal move), q int64 [n, 4] (INT64_MIN:
-        illegal), legal uint8 [n])."""
+        illegal), legal uint8 [n]).  With downgrade, q belongs to the translated boards (the class docstring);
+        best and legal hold for the boards given."""
         bufs = self._buffers(boards.shape[0])
         self._search(boards, 0, bufs)
         return bufs[:3]

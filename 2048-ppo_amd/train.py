@@ -544,16 +544,59 @@ def play_ntuple(model_path: Path = typer.Argument(..., metavar="MODEL", help="a 
                 games: int = typer.Option(100, "--games", "-g"),
                 max_moves: Optional[int] = typer.Option(None, "--max-moves",
                                                         help="stop every game after this many moves"),
-                depth: int = typer.Option(1, "--depth", help="moves looked ahead, the root move included (1..3)")):
+                depth: int = typer.Option(1, "--depth", help="moves looked ahead, the root move included (1..3)"),
+                downgrade_from: Optional[int] = typer.Option(None, "--downgrade-from", metavar="TILE",
+                                                             help="tile-downgrading: on a board whose largest tile "
+                                                                  "is at least TILE (4..32768) and that lacks a tile "
+                                                                  "value below it, choose the move on the board with "
+                                                                  "every tile above that gap halved; absent: off"),
+                downgrade_lo: Optional[int] = typer.Option(None, "--downgrade-lo", metavar="TILE",
+                                                           help="the smallest missing tile value that counts as a "
+                                                                "gap (2..TILE / 2 of --downgrade-from; default 2)"),
+                downgrade_rounds: Optional[int] = typer.Option(None, "--downgrade-rounds", metavar="R",
+                                                               help="halve at most R times, a gap at a time (1..16; "
+                                                                    "default 1)"),
+                reach: str = typer.Option("", "--reach", metavar="TILES",
+                                          help="tile values, e.g. 4096,8192,16384,32768: print one more line with "
+                                               "the share of games that reached each of them")):
     """Play `games` seeded games (game i spawns like random.seed(i), as `evaluate`) with the greedy
     player of a trained n-tuple network, or with --depth 2 or 3 its expectimax player: the same values
-    at the leaves of a search over every move and spawn."""
-    from g2048.ntuple import MAX_SEARCH_DEPTH, NTupleNet, NTuplePlayer
+    at the leaves of a search over every move and spawn.  --downgrade-from TILE lets the player choose on the
+    tile-downgraded board once a TILE is on it (Guei et al. 2021: a board with tiles the net has hardly seen is
+    read as the same ladder one rung lower); the games and their scores stay those of the real boards.  --reach
+    adds a line with the share of games whose largest tile reached each listed value."""
+    from g2048.ntuple import MAX_SEARCH_DEPTH, NTupleNet, NTuplePlayer, downgrade_params
     if not 1 <= depth <= MAX_SEARCH_DEPTH:
         typer.echo(f"Error: --depth must be in 1..{MAX_SEARCH_DEPTH}, got {depth}")
         raise typer.Exit(1)
-    player = NTuplePlayer(NTupleNet.load(model_path, torch.device("cuda", 0)), depth)
-    _echo_results(player.play_games(games, max_moves, seeds=list(range(games))))
+    downgrade = None
+    if downgrade_from is None:
+        for opt, v in (("--downgrade-lo", downgrade_lo), ("--downgrade-rounds", downgrade_rounds)):
+            if v is not None:
+                typer.echo(f"Error: {opt} needs --downgrade-from")
+                raise typer.Exit(1)
+    else:
+        downgrade = (downgrade_from, 2 if downgrade_lo is None else downgrade_lo,
+                     1 if downgrade_rounds is None else downgrade_rounds)
+        try:
+            downgrade_params(*downgrade)
+        except ValueError as e:
+            typer.echo(f"Error: --downgrade-from / --downgrade-lo / --downgrade-rounds: {e}")
+            raise typer.Exit(1)
+    try:
+        reach_list = [int(v) for v in reach.split(",") if v.strip()]
+    except ValueError:
+        reach_list = None
+    if reach_list is None or any(v < 2 or v > 131072 or v & (v - 1) for v in reach_list):
+        typer.echo(f"Error: --reach must be tile values, powers of two in 2..131072, got {reach}")
+        raise typer.Exit(1)
+    player = NTuplePlayer(NTupleNet.load(model_path, torch.device("cuda", 0)), depth, downgrade=downgrade)
+    res = player.play_games(games, max_moves, seeds=list(range(games)))
+    _echo_results(res)
+    if reach_list:
+        tiles = res["max_tiles"]
+        typer.echo("Tiles Reached (--reach) - " + ", ".join(
+            f"{v}: {sum(1 for t in tiles if t >= v) / len(tiles) * 100:.1f}%" for v in reach_list))
 
 
 @app.command("export-demo")

@@ -213,6 +213,36 @@
  * With base == 0 it is g2048_ntuple_promote byte for byte.  On a stage that still holds base everywhere it is a
  * copy of W[from]; on one that has learned d[j] over base it leaves base + d[j] + (W[from][j] - base): what both
  * stages learned, over one start.  The accumulators of rule TC are not touched, as in g2048_ntuple_promote.
+ *
+ * Tile-downgrading (g2048_ntuple_downgrade; Guei, Chen, Wu 2021; tests/ntuple_downgrade_reference.py).  A net is
+ * only as good as the boards it was trained on, and the tables indexed by the largest tiles are trained last and
+ * least: a player that reaches such a tile reads weights that still hold their start.  The large tiles of a board
+ * are mostly a ladder, and the net knows how to play a ladder one rung lower.  So when a tile value is missing
+ * below the largest tile, every tile above that gap is halved, and the player chooses its move on the translated
+ * board.  It is a pure map from 16 bytes to 16 bytes; nothing of the net takes part.
+ * Parameters: from_exp f in 2..31, lo_exp l in 1..f - 1, rounds R in 1..16.  A cell is read as its unsigned byte u.
+ * Cells with u > 31 take no part: they are not counted in P and are copied unchanged, so the rule is total on any
+ * 16 bytes.  One round on a board:
+ *   P = the set of the values 1..31 present on the board;  m = max P, 0 for an empty P
+ *   if m < f: the board is done
+ *   j = the largest value with l <= j < m that is not in P; if there is none: the board is done
+ *   every cell with j < u <= 31 becomes u - 1
+ * Rounds repeat until the board is done, and at most R times.  shift[i] = the number of rounds applied to board i.
+ * What follows, per round applied and so for the whole map:
+ *   m falls by exactly one: j < m, so the cells holding m are decremented, and nothing above m exists in P.
+ *   For any two cells, <, == and > between their values are the same before and after: j was absent, so
+ *   j + 1 -> j collides with nothing, and u -> u - [u > j] is strictly increasing on the values present (cells
+ *   with u > 31 stay above every cell that takes part).
+ *   Empty cells stay empty (j >= l >= 1), and cells with a value <= j are untouched.
+ *   Hence the legal-move mask of the translated board is that of the original, move(., a) moves the same tiles
+ *   to the same cells (move(D(b), a) = D(move(b, a)) cell for cell, D the map u -> u - [j < u <= 31] of the
+ *   round), and a best chosen on the translated board is a legal action of the original.
+ *   shift == 0 leaves the board byte for byte.
+ *   f = 15, l = 1, R = 1 is the rule of the paper (once a 32768 is on the board): 32768, 16384, 8192, 2048 becomes
+ *   16384, 8192, 4096, 2048.
+ * What is NOT preserved: the merge points of halved tiles are halved; deeper in a search a merge into the value j
+ * can meet the former j + 1, which the original board would not merge.  So the q of a translated board are values
+ * of that board: useful for ranking the moves, not scores of the original.
  */
 #ifndef G2048_NTUPLE_H
 #define G2048_NTUPLE_H
@@ -385,6 +415,14 @@ int g2048_ntuple_staged_fill(g2048_stream_t stream, const g2048_ntuple_staged_ne
    is g2048_ntuple_promote.  The refusals are g2048_ntuple_promote's. */
 int g2048_ntuple_promote_from(g2048_stream_t stream, const g2048_ntuple_staged_net *net, int32_t from, int32_t to,
                               int32_t base);
+
+/* ---- tile-downgrading (Tile-downgrading, above): out[i] = boards[i] after at most `rounds` rounds with from_exp
+   and lo_exp, shift[i] (nullable, uint8 [n]) = the rounds applied.  boards / out int8 [n,16], 16-B aligned;
+   out == boards is allowed (in place: every board is read and written by its own lane only), any other overlap is
+   not.  One launch, no workspace.  0 <= n < 2^31.  G2048_EINVAL for from_exp outside 2..31, lo_exp outside
+   1..from_exp - 1, rounds outside 1..16, n out of range, null or misaligned boards or out. */
+int g2048_ntuple_downgrade(g2048_stream_t stream, const int8_t *boards, int8_t *out, uint8_t *shift, int64_t n,
+                           int32_t from_exp, int32_t lo_exp, int32_t rounds);
 
 #ifdef __cplusplus
 }
